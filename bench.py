@@ -21,8 +21,12 @@ native LLM engine at TP = N (see shai_amd.engines.llm).
 flux T = 1 (one replica per GPU).  ``--workload flux --tp 8`` is the reference's Flux TP8 latency setup
 (cova/README.md:98).
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--tp T]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--tp T] [--full] [--dump-outputs DIR]
         python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+A plain run sets up, runs W warm-up and K timed steps and prints the result line.  ``--full`` adds the measurements
+the headline figure does not need: the p50 latency of single requests (``--latency-runs``) and, for flux / mllama /
+t5, the ``vs_baseline`` derived from it; without it those fields are null.  ``--dump-outputs DIR`` writes what the
+last timed step returned as ``DIR/<name>.npy`` (inputs and weights are seeded, so equal arguments give equal inputs).
 ``python bench.py --gpus N`` with N > 1 outside a launcher re-runs itself under torch.distributed.run with N
 ranks (a child process, started before this process touches the GPU).  Prints ONE JSON line on rank 0.
 """
@@ -116,6 +120,29 @@ def _max_over_ranks(x, world):
     return float(t.item())
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # --dump-outputs: all arrays of one run together, as float32
+
+
+def _dump_outputs(out_dir, outputs):
+    """Write each array the last timed step returned (rank 0's) as ``out_dir/<name>.npy`` in float32.  An array
+    over its share of the budget is written as a sample: its flattened elements at sorted indices drawn from
+    ``numpy.random.default_rng(0)``, the same for every run of the same shape."""
+    import numpy as np
+    import torch
+    if not outputs:
+        raise SystemExit("--dump-outputs: the workload returned no outputs")
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // len(outputs)
+    for name, x in outputs.items():
+        if isinstance(x, torch.Tensor):
+            x = x.detach().float().cpu().numpy()
+        a = np.ascontiguousarray(x, dtype=np.float32)
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, share))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def bench_sd21(args, rank, world):
     import torch
     from shai_amd.engines.diffusion import SDConfig, StableDiffusionEngine
@@ -127,7 +154,7 @@ def bench_sd21(args, rank, world):
         eng.generate(prompts, args.inference_steps, seed=1000 + i, output="tensor")
     # p50 single-image latency (reference's request latency semantics), outside the timed region
     lat = []
-    for i in range(args.latency_runs):
+    for i in range(args.latency_runs if args.full else 0):
         _sync()
         t0 = time.perf_counter()
         eng.generate(prompts[:1], args.inference_steps, seed=2000 + i)
@@ -144,6 +171,7 @@ def bench_sd21(args, rank, world):
     _barrier(world)
     elapsed = _max_over_ranks(time.perf_counter() - t0, world)
     ok = bool(torch.isfinite(img.float()).all().item())
+    args.outputs = {"images": img}
     images = args.batch * args.steps * world
     value = images / elapsed
     res = {
@@ -193,7 +221,7 @@ def bench_flux(args, rank, world):
     for i in range(args.warmup):
         eng.generate(prompts, steps_inf, seed=10 + i, output="tensor")
     lat = []
-    for i in range(args.latency_runs):
+    for i in range(args.latency_runs if args.full else 0):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         eng.generate(prompts[:1], steps_inf, seed=20 + i)
@@ -208,6 +236,7 @@ def bench_flux(args, rank, world):
     elapsed = _max_over_ranks(time.perf_counter() - t0, world)
     value = args.batch * args.steps * replicas / elapsed
     p50 = statistics.median(lat) if lat else None
+    args.outputs = {"images": img}
     return {
         "metric": f"Flux.1-dev {args.height}x{args.width} images/sec ({steps_inf} steps)",
         "value": round(value, 4), "unit": "images/s", "n_gpus": world, "steps": args.steps,
@@ -256,7 +285,7 @@ def bench_mllama(args, rank, world):
         while eng.has_work():
             eng.step()
     lat = []
-    for _ in range(args.latency_runs):
+    for _ in range(args.latency_runs if args.full else 0):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         s = eng.add_request(prompt, params, image=pre)
@@ -307,7 +336,7 @@ def bench_vit(args, rank, world):
     for _ in range(max(1, args.warmup)):
         eng.logits_u8(imgs).argmax(-1).cpu()
     lat = []
-    for _ in range(args.latency_runs):  # single-image request latency (reference semantics), untimed
+    for _ in range(args.latency_runs if args.full else 0):  # single-image request latency (--full), untimed
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         eng.logits_u8(imgs[:1]).argmax(-1).cpu()
@@ -319,6 +348,7 @@ def bench_vit(args, rank, world):
     _barrier(world)
     elapsed = _max_over_ranks(time.perf_counter() - t0, world)
     value = args.batch * args.steps * world / elapsed
+    args.outputs = {"labels": labels}
     return {
         "metric": "ViT-base/16 224x224 images/sec (image classification)", "value": round(value, 2),
         "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -354,7 +384,7 @@ def bench_t5(args, rank, world):
         eng.embed(texts, L)
         eng.embed(texts[:1], L)
     lat = []
-    for _ in range(max(args.latency_runs, 5)):  # single-request latency (reference semantics), untimed
+    for _ in range(max(args.latency_runs, 5) if args.full else 0):  # single-request latency (--full), untimed
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         e = eng.embed(texts[:1], L)
@@ -365,16 +395,17 @@ def bench_t5(args, rank, world):
         e = eng.embed(texts, L)
     _barrier(world)
     elapsed = _max_over_ranks(time.perf_counter() - t0, world)
-    p50 = statistics.median(lat)
+    p50 = statistics.median(lat) if lat else None
+    args.outputs = {"embeddings": e}
     return {
         "metric": "T5-v1.1-large embeddings/sec (mean-pooled, %d tokens)" % L, "value": round(args.batch * args.steps * world / elapsed, 2),
         "unit": "embeddings/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(1000 * elapsed / args.steps, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": round(REF_T5_CAPTION_S / p50, 3), "dtype": "bf16",
+        "vs_baseline": round(REF_T5_CAPTION_S / p50, 3) if p50 else None, "dtype": "bf16",
         "data": "synthetic caption, random-init weights (full T5-v1.1-large encoder)",
         "config": {"model": "google/t5-v1_1-large (encoder architecture)", "global_batch": args.batch * world,
                    "per_gpu_batch": args.batch, "seq_len": L, "parallelism": f"dp{world}"},
-        "p50_latency_ms_bs1": round(1000 * p50, 2),
+        "p50_latency_ms_bs1": round(1000 * p50, 2) if p50 else None,
         "embedding_dim": int(e.shape[-1]), "outputs_finite": bool(np.isfinite(e).all()),
         "baseline_note": "vs_baseline = 0.20 s (reference T5 caption embedding latency, inf2, cova/README.md:98) / our "
                          "p50 single-request latency",
@@ -401,7 +432,14 @@ def main():
     ap.add_argument("--width", type=int, default=512)
     ap.add_argument("--quantization", default=None, choices=[None, "fp8"],
                     help="mistral: fp8 e4m3 weight-only quantisation (NOT the bf16 headline config)")
-    ap.add_argument("--latency-runs", type=int, default=3)
+    ap.add_argument("--latency-runs", type=int, default=3,
+                    help="--full only: untimed single-request runs behind p50_latency_ms_bs1")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (the single-request p50 latency and "
+                         "the vs_baseline figures derived from it); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; "
+                         "outputs over the size budget as a fixed seeded sample of their elements)")
     ap.add_argument("--no-graphs", action="store_true")
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--gen-len", type=int, default=128)
@@ -420,6 +458,9 @@ def main():
         _relaunch(args.gpus)
     if args.tp is None:
         args.tp = args.gpus if args.workload in ("mistral", "mllama") else 1
+    if args.dump_outputs and args.workload in ("mistral", "mllama"):
+        raise SystemExit(f"--dump-outputs is not implemented for --workload {args.workload}")
+    args.outputs = {}
     if args.batch is None:  # dynamic-batching caps a serving replica would use for each workload
         args.batch = {"sd21": 32, "mistral": 64, "flux": 1, "mllama": 8, "vit": 32, "t5": 32}[args.workload]
     import torch
@@ -431,6 +472,8 @@ def main():
     if DEVICE == "cpu":
         res["data"] = "CPU DRY RUN (tiny config, gloo): plumbing check, not a measurement"
     if rank == 0:
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, args.outputs)
         print(json.dumps(res), flush=True)
         save = os.environ.get("SHAI_GEMM_TUNE_SAVE")
         if save:

@@ -16,7 +16,9 @@ pytestmark = pytest.mark.slow
 
 def _fleet(tmp_path, module, extra_env, tps=(1, 2), restart=False):
     from shai_amd.supervisor import GPUInventory, Supervisor, WorkerSpec
-    sup = Supervisor(None, GPUInventory(list(range(2 * len(tps)))), log_dir=str(tmp_path))  # slots, not GPUs
+    # slots, not GPUs: numbered past any real device, so the HIP_VISIBLE_DEVICES the supervisor pins each CPU worker
+    # with never names more GPUs than the machine running the test shows (torch's launcher rejects that)
+    sup = Supervisor(None, GPUInventory(list(range(64, 64 + 2 * len(tps)))), log_dir=str(tmp_path))
     env = {"DEVICE": "cpu", "SHAI_MODEL_CONFIG": "tiny", "OMP_NUM_THREADS": "2", "SHAI_TP_HEARTBEAT_S": "1"}
     env.update(extra_env)
     names = []

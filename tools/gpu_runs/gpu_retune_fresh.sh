@@ -10,10 +10,10 @@ mkdir -p gpurun_out
 OUT=gpurun_out/gemm_tuning_fresh.json
 echo "[]" > $OUT
 export SHAI_GEMM_TUNE_FILE=$OUT SHAI_GEMM_TUNE_SAVE=$OUT
-for spec in "sd21:--workload sd21 --steps 1 --warmup 1 --latency-runs 1" \
+for spec in "sd21:--workload sd21 --steps 1 --warmup 1 --full --latency-runs 1" \
             "sd21b16:--workload sd21 --batch 16 --steps 1 --warmup 1 --latency-runs 0" \
-            "flux:--workload flux --steps 1 --warmup 1 --latency-runs 1" \
-            "mllama:--workload mllama --steps 1 --warmup 1 --latency-runs 1" \
+            "flux:--workload flux --steps 1 --warmup 1 --full --latency-runs 1" \
+            "mllama:--workload mllama --steps 1 --warmup 1 --full --latency-runs 1" \
             "mistral64:--workload mistral --steps 1 --warmup 1 --batch 64" \
             "mistral32:--workload mistral --steps 1 --warmup 1 --batch 32"; do
   wl=${spec%%:*}; args=${spec#*:}

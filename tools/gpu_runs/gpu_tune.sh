@@ -10,11 +10,11 @@ T=gpurun_out/gemm_tuning_mi355x.json
 export SHAI_GEMM_TUNE_FILE=$T SHAI_GEMM_TUNE_SAVE=$T
 for wl in "$@"; do
   case $wl in
-    sd21)    args="--workload sd21 --steps 1 --warmup 1 --latency-runs 1" ;;
+    sd21)    args="--workload sd21 --steps 1 --warmup 1 --full --latency-runs 1" ;;
     mistral) args="--workload mistral --steps 1 --warmup 1 --batch 32" ;;
     mistral64) args="--workload mistral --steps 1 --warmup 1 --batch 64" ;;
-    flux)    args="--workload flux --steps 1 --warmup 1 --latency-runs 1 --batch 1" ;;
-    mllama)  args="--workload mllama --steps 1 --warmup 1 --latency-runs 1 --batch 8" ;;
+    flux)    args="--workload flux --steps 1 --warmup 1 --full --latency-runs 1 --batch 1" ;;
+    mllama)  args="--workload mllama --steps 1 --warmup 1 --full --latency-runs 1 --batch 8" ;;
   esac
   timeout -k 10 900 python -u bench.py $args > gpurun_out/tune_$wl.log 2>&1
   rc=$?
