@@ -71,7 +71,7 @@ std::unordered_map<std::string, Choice> g_tuned;
 
 bool lib_supported(const shai::GemmArgs& g) {
   return g.conv == 0 && !g.row_mr && g.batch <= 1 && !g.w_slice_rows && !g.glu && g.act == 0 && !g.bias2d && !g.gate &&
-         !g.rms && !g.w_scale &&
+         !g.rms && !shai::quantized_w(g) &&
          !g.A2 && !g.in_scale && g.alpha == 1.f && !(g.bias && g.residual) &&
          (!g.residual || (g.res_alpha == 1.f && g.residual == g.C && g.ldr == g.ldc)) &&
          g.lda >= g.K && g.ldw >= g.K && g.ldc >= g.N;
@@ -84,7 +84,7 @@ std::string gemm_key(const shai::GemmArgs& g) {
   // library-eligible problems (plain GEMM, bias at most) race hipBLASLt in the tuner, so their winner must
   // not be reused by a same-shape problem with a fused epilogue (and vice versa): separate key class
   // a folded-LayerNorm GEMM (row_mr) runs only unsplit on v4: it tunes and caches apart from the plain problem
-  return std::string(buf) + (g.rms ? "|rms" : "") + (g.w_scale ? "|fp8w" : "") + (g.row_mr ? "|ln" : "") +
+  return std::string(buf) + (g.rms ? "|rms" : "") + (g.w_scale ? "|fp8w" : "") + (g.w_mx_scale ? "|mxfp4w" : "") + (g.row_mr ? "|ln" : "") +
          (g.w_slice_rows ? "|wslice" + std::to_string(g.w_slice_rows) : "") +
          (lib_supported(g) && !g.residual ? "|lib" : "");
 }
@@ -212,6 +212,19 @@ void launch_skinny2_choice(const shai::GemmArgs& g, const Tensor& like, int kg, 
   shai::launch_skinny2(g, wsp, kg, deep, stream());
 }
 
+// MXFP4 weights (csrc/kernels/gemv_fp4.hip): the only kernel of such a problem.  Its choices reuse kSkinnyCfg (split-K
+// with the separate fold) and kSkinnyFixCfg (in-launch fixup) under the problem's own "|mxfp4w" key.
+void launch_skinny_fp4_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
+  Tensor ws;
+  float* wsp = nullptr;
+  const size_t bytes = shai::skinny_fp4_workspace_bytes(g, kg);
+  if (bytes > 0) {
+    ws = at::empty({(long)(bytes / sizeof(float))}, like.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  shai::launch_skinny_fp4(g, wsp, kg, fixup, stream());
+}
+
 void launch_skinny_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
   Tensor ws;
   float* wsp = nullptr;
@@ -245,6 +258,11 @@ void launch_lib(const shai::GemmArgs& g, const Tensor& like) {
 }
 
 void launch_choice(const shai::GemmArgs& g, const Tensor& like, Choice c) {
+  if (g.w_mx_scale != nullptr) {
+    SHAI_CHECK(shai::skinny_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 skinny kernel");
+    launch_skinny_fp4_choice(g, like, c.splits, c.cfg == kSkinnyFixCfg);
+    return;
+  }
   if (c.cfg == kLibCfg) {
     if (lib_supported(g)) {
       launch_lib(g, like);
@@ -305,8 +323,15 @@ Choice tune(const shai::GemmArgs& g_real, const Tensor& like, bool skinny_only =
   g.C = reinterpret_cast<shai::bf16_t*>(scratch.data_ptr());
   g.ldc = n_out;
   g.batch_c = (long)g.M * n_out;
-  Choice def{kSkinnyCfg, shai::skinny_kgroups(g)};
+  Choice def{kSkinnyCfg, g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g)};
   std::vector<Choice> cands;
+  if (g.w_mx_scale != nullptr) {
+    skinny_only = true;
+    for (int kg = 1; kg <= shai::skinny_fp4_max_kgroups(g); kg *= 2) {
+      cands.push_back({kSkinnyCfg, kg});
+      if (kg > 1) cands.push_back({kSkinnyFixCfg, kg});
+    }
+  }
   if (!skinny_only) {
     shai::gemm2_plan(g, &def.cfg, &def.splits);
     const int ms = max_splits_for(g);
@@ -337,7 +362,7 @@ Choice tune(const shai::GemmArgs& g_real, const Tensor& like, bool skinny_only =
   // Decode-shaped problems (M <= 64) stream weights that are NOT cache resident in a real decode step (the
   // model's weights are tens of GB; the MALL holds 256 MB): each timed launch runs behind a flush of the
   // Infinity Cache so the candidates are ranked by their HBM-streaming speed, not by a warm-cache replay.
-  const bool cold = g.M <= 64 && (long)g.N * g.K * (g.w_scale ? 1 : 2) >= (4L << 20);
+  const bool cold = g.M <= 64 && (long)g.N * g.K * (g.w_scale ? 2 : g.w_mx_scale ? 1 : 4) / 2 >= (4L << 20);
   for (const Choice& c : cands) {
     launch_choice(g, like, c);  // warm (also instantiates caches)
     float ms = 0.f;
@@ -381,7 +406,7 @@ void run_skinny(const shai::GemmArgs& g, const Tensor& like) {
       c = tune(g, like, true);
       store_choice(g, key, c);
     } else {
-      c = Choice{kSkinnyCfg, shai::skinny_kgroups(g)};
+      c = Choice{kSkinnyCfg, g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g)};
     }
   }
   launch_choice(g, like, c);
@@ -768,6 +793,73 @@ void attach_norm_io(shai::GemmArgs& g, const optional<Tensor>& ln_mr, const opti
   }
 }
 
+// MXFP4 weights (ops.quantize_mxfp4): w float4_e2m1fn_x2 [N, K / 2] (two codes per byte), w_scale e8m0 bytes tiled per
+// 128-wide K step, [ceil(K / 128), N, 4]; decode-shaped activations a [M <= 64, K] only (larger problems dequantise).
+// force_cfg (tests / tools; < 0: tuned per shape): 1000 = the heuristic K-group count with the separate fold,
+// 1000 + kg = kg K groups folded by the separate kernel (1001 = no split), 1100 + kg = kg K groups fixed up inside
+// the launch -- the numbers of the bf16 / fp8 skinny kernel, here always on gemv_fp4.hip (1 <= kg <= 64).
+void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
+                const optional<Tensor>& residual, double alpha, double res_alpha, int64_t act, bool glu,
+                int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale) {
+  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(0) <= 64 && a.size(1) >= 32 && a.size(1) % 32 == 0,
+             "mxfp4 gemm: decode-shaped activations only (1 <= M <= 64, K % 32 == 0); dequantize for larger M");
+  const long M = a.size(0), K = a.size(1);
+  SHAI_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() && w.size(1) * 2 == K &&
+                 reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+             "mxfp4 gemm: w must be a contiguous, 16-byte aligned float4_e2m1fn_x2 [N, K / 2] matrix, got ", w.sizes(),
+             " for K = ", K);
+  const long N = w.size(0);
+  SHAI_CHECK(w_scale.has_value(), "mxfp4 gemm: w_scale (the e8m0 group scales of quantize_mxfp4) is required");
+  const Tensor& sc = *w_scale;
+  SHAI_CHECK(sc.is_cuda() && sc.get_device() == w.get_device() &&
+                 (sc.scalar_type() == at::ScalarType::Float8_e8m0fnu || sc.scalar_type() == at::kByte) &&
+                 sc.is_contiguous() && sc.dim() == 3 && sc.size(0) == (K + 127) / 128 && sc.size(1) == N &&
+                 sc.size(2) == 4 && reinterpret_cast<uintptr_t>(sc.data_ptr()) % 4 == 0,
+             "mxfp4 gemm: w_scale must be contiguous float8_e8m0fnu [ceil(K / 128), N, 4], got ", sc.sizes());
+  check_bf16(c, "c");
+  SHAI_CHECK(N % 2 == 0 && (!glu || N % 4 == 0), "mxfp4 gemm: N must be even (glu: N % 4 == 0)");
+  SHAI_CHECK(c.dim() == 2 && c.size(0) == M && c.size(1) == (glu ? N / 2 : N), "gemm output shape mismatch ", c.sizes());
+  shai::GemmArgs g{};
+  g.A = cptr(a);
+  g.W = reinterpret_cast<const shai::bf16_t*>(w.data_ptr());
+  g.w_mx_scale = reinterpret_cast<const uint8_t*>(sc.data_ptr());
+  g.C = mptr(c);
+  g.M = (int)M;
+  g.K = (int)K;
+  g.N = (int)N;
+  g.lda = a.stride(0);
+  g.ldw = K / 2;  // bytes
+  g.ldc = c.stride(0);
+  g.batch = 1;
+  if (bias) {
+    check_bf16(*bias, "bias");
+    SHAI_CHECK(bias->numel() == N, "bias size");
+    g.bias = cptr(*bias);
+  }
+  if (residual) {
+    check_bf16(*residual, "residual");
+    SHAI_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == c.size(1), "residual shape");
+    g.residual = cptr(*residual);
+    g.ldr = residual->stride(0);
+  }
+  g.alpha = alpha;
+  g.res_alpha = res_alpha;
+  g.act = act;
+  g.glu = glu;
+  if (rms_eps >= 0) {
+    g.rms = 1;
+    g.rms_eps = (float)rms_eps;
+  }
+  SHAI_CHECK(shai::skinny_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 skinny kernel");
+  SHAI_CHECK(force_cfg < 0 || (force_cfg >= kSkinnyCfg && force_cfg <= kSkinnyCfg + 64) ||
+                 (force_cfg > kSkinnyFixCfg && force_cfg <= kSkinnyFixCfg + 64),
+             "mxfp4 gemm: force_cfg must be 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
+  if (force_cfg > kSkinnyFixCfg) launch_choice(g, a, Choice{kSkinnyFixCfg, (int)(force_cfg - kSkinnyFixCfg)});
+  else if (force_cfg > kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, (int)(force_cfg - kSkinnyCfg)});
+  else if (force_cfg == kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, shai::skinny_fp4_kgroups(g)});
+  else run_skinny(g, a);
+}
+
 // a: [M, K] or [B, M, K]; w: [N, K] or [B, N, K]; c: [M, N'] or [B, M, N'] (N' = N or N/2 for glu)
 void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
           const optional<Tensor>& bias2d, int64_t rows_per_bias2d, const optional<Tensor>& residual, double alpha,
@@ -776,6 +868,12 @@ void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tens
           const optional<Tensor>& ln_s, const optional<Tensor>& gn_part, const optional<Tensor>& ln_stats,
           double ln_eps, int64_t w_slice_rows) {
   check_rows(a, "a");
+  if (w.scalar_type() == at::ScalarType::Float4_e2m1fn_x2) {
+    SHAI_CHECK(!bias2d && !gate && !ln_mr && !ln_s && !gn_part && !ln_stats && w_slice_rows == 0,
+               "mxfp4 gemm: bias / activation / GLU / residual / folded RMSNorm epilogues only");
+    gemm_mxfp4(a, w, c, bias, residual, alpha, res_alpha, act, glu, force_cfg, rms_eps, w_scale);
+    return;
+  }
   if (w_scale.has_value()) {  // fp8 (e4m3) weights + fp32 per-row scale: skinny (decode-shaped) kernel only
     SHAI_CHECK(w.is_cuda() && w.scalar_type() == at::kFloat8_e4m3fn && w.dim() == 2 && w.stride(1) == 1 &&
                    w.stride(0) % 16 == 0,
@@ -1552,6 +1650,26 @@ void dequant_fp8(const Tensor& w8, const Tensor& scale, const Tensor& out) {
                                 w8.size(0), w8.size(1), stream());
 }
 
+// wq: float4_e2m1fn_x2 [N, K / 2], scales: e8m0 bytes [ceil(K / 128), N, 4] (ops.quantize_mxfp4) -> out bf16 [N, K]
+void dequant_mxfp4(const Tensor& wq, const Tensor& scales, const Tensor& out) {
+  SHAI_CHECK(wq.is_cuda() && wq.scalar_type() == at::ScalarType::Float4_e2m1fn_x2 && wq.dim() == 2 &&
+                 wq.is_contiguous() && wq.size(1) % 16 == 0 && reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0,
+             "dequant_mxfp4: wq must be a contiguous, 16-byte aligned float4_e2m1fn_x2 [N, K / 2], K % 32 == 0");
+  const long N = wq.size(0), K = wq.size(1) * 2;
+  SHAI_CHECK(scales.is_cuda() && scales.get_device() == wq.get_device() &&
+                 (scales.scalar_type() == at::ScalarType::Float8_e8m0fnu || scales.scalar_type() == at::kByte) &&
+                 scales.is_contiguous() && scales.dim() == 3 && scales.size(0) == (K + 127) / 128 &&
+                 scales.size(1) == N && scales.size(2) == 4,
+             "dequant_mxfp4: scales must be contiguous float8_e8m0fnu [ceil(K / 128), N, 4], got ", scales.sizes());
+  check_bf16(out, "out");
+  SHAI_CHECK(out.is_contiguous() && out.dim() == 2 && out.size(0) == N && out.size(1) == K &&
+                 out.get_device() == wq.get_device(),
+             "dequant_mxfp4: out must be a contiguous bf16 [N, K]");
+  SHAI_CHECK(K < (1L << 31), "dequant_mxfp4: K too large");
+  shai::launch_dequant_mxfp4(reinterpret_cast<const uint8_t*>(wq.data_ptr()),
+                             reinterpret_cast<const uint8_t*>(scales.data_ptr()), mptr(out), N, (int)K, stream());
+}
+
 // y = a w^T + bias + res_alpha residual into c, and LayerNorm(y) gamma + beta into c2, on the W-stationary kernel
 // (gemm_ws.hip: K = 320, N = 320, the row moments from the epilogue's registers).  Returns false (nothing launched)
 // when the problem is outside the kernel's contract; the caller then runs the GEMM and the norm separately.
@@ -1674,6 +1792,7 @@ TORCH_LIBRARY(shai, m) {
   m.def("row_moments(Tensor x, Tensor(a!) mr, float eps) -> ()");
   m.def("gemm(Tensor a, Tensor w, Tensor(a!) c, Tensor? bias, Tensor? bias2d, int rows_per_bias2d, Tensor? residual, float alpha, float res_alpha, int act, bool glu, Tensor? gate=None, int rows_per_gate=1, int force_cfg=-1, float rms_eps=-1.0, Tensor? w_scale=None, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, int w_slice_rows=0) -> ()");
   m.def("dequant_fp8(Tensor w8, Tensor scale, Tensor(a!) out) -> ()");
+  m.def("dequant_mxfp4(Tensor wq, Tensor scales, Tensor(a!) out) -> ()");
   m.def("layernorm_mod(Tensor x, Tensor scale, Tensor shift, Tensor(a!) out, int rows_per_mod, float eps) -> ()");
   m.def("qk_norm_rope(Tensor(a!) x, Tensor? q_w, Tensor? k_w, Tensor? cos, Tensor? sin, int H, int D, int S, float eps) -> ()");
   m.def("conv2d(Tensor x, Tensor? x2, Tensor w, Tensor(a!) out, Tensor? bias, Tensor? bias2d, Tensor? residual, Tensor? in_scale, Tensor? in_shift, int in_act, int kh, int kw, int stride, int pad, bool upsample, int act, float res_alpha, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, bool up_phases=False) -> ()");
@@ -1715,6 +1834,7 @@ TORCH_LIBRARY_IMPL(shai, CUDA, m) {
   m.impl("groupnorm_apply", &groupnorm_apply);
   m.impl("gemm", &gemm);
   m.impl("dequant_fp8", &dequant_fp8);
+  m.impl("dequant_mxfp4", &dequant_mxfp4);
   m.impl("gemm_f8", &gemm_f8);
   m.impl("gemm_lnout", &gemm_lnout);
   m.impl("quant_rows_fp8", &quant_rows_fp8);

@@ -486,7 +486,7 @@ bool conv_halo_supported(const GemmArgs& a) {
   if (a.M != a.Nimg * a.OH * a.OW || a.M % HC_BM != 0) return false;
   if (a.Cin % 64 != 0 || (a.A2 != nullptr && (a.Cin1 % 64 != 0 || a.Cin1 <= 0))) return false;
   if (hc_bn(a) == 0) return false;
-  if (a.act != ACT_NONE || a.glu || a.gate || a.rms || a.w_scale || a.row_mr || a.alpha != 1.f) return false;
+  if (a.act != ACT_NONE || a.glu || a.gate || a.rms || quantized_w(a) || a.row_mr || a.alpha != 1.f) return false;
   if (a.in_scale != nullptr) {
     // GroupNorm + SiLU (the only normalised variant instantiated); scale and shift in one allocation
     if (a.in_act != ACT_SILU || a.upsample || a.in_shift != a.in_scale + (long)a.Nimg * a.Cin) return false;

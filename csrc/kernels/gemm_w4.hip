@@ -408,7 +408,7 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(const GemmArgs p) {
 }
 
 bool gemm_w4_supported(const GemmArgs& a) {
-  if (a.in_scale != nullptr || a.rms || a.w_scale != nullptr || (a.glu && a.N % 8 != 0)) return false;
+  if (a.in_scale != nullptr || a.rms || quantized_w(a) || (a.glu && a.N % 8 != 0)) return false;
   if (a.K % 8 != 0 || a.lda % 8 != 0 || a.ldw % 8 != 0) return false;  // 16-B source chunks
   if ((long)a.N * a.ldw * 2 >= 0x7fffffffL) return false;
   if (a.conv) {

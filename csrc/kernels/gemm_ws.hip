@@ -612,7 +612,7 @@ __global__ void __launch_bounds__(256, 1) gemm_ws_kernel(const GemmArgs p, int s
 
 // ---------------------------------------------------------------------------- host side
 bool gemm_ws_supported(const GemmArgs& a) {
-  if (a.conv || a.batch > 1 || a.A2 || a.in_scale || a.rms || a.w_scale || a.gate || a.bias2d) return false;
+  if (a.conv || a.batch > 1 || a.A2 || a.in_scale || a.rms || quantized_w(a) || a.gate || a.bias2d) return false;
   if (a.K != 320 || a.N % WS_BN != 0 || a.M <= 0) return false;
   if (a.glu && a.residual) return false;
   if (a.lda % 8 || a.ldw % 8 || a.ldc % 8 || (a.residual && a.ldr % 8)) return false;

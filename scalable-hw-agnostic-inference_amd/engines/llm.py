@@ -355,8 +355,13 @@ class LLMEngine:
         if self.quantization == "fp8":
             from ..parallel.layers import quantize_fp8_
             quantize_fp8_(self.model)
+        elif self.quantization == "mxfp4":
+            # OCP MXFP4 weight-only (e2m1 codes + e8m0 scale per 32 along K): a quarter of the bf16 weight bytes
+            from ..parallel.layers import quantize_mxfp4_
+            quantize_mxfp4_(self.model)
         elif self.quantization not in (None, "none", "bf16"):
-            raise ValueError(f"quantization={quantization!r}: supported: fp8 (weight-only e4m3) or none")
+            raise ValueError(f"quantization={quantization!r}: supported: fp8 (weight-only e4m3), mxfp4 (weight-only "
+                             "e2m1 + e8m0 group scales) or none")
         self.max_num_seqs = max_num_seqs
         self.max_model_len = min(max_model_len, cfg.max_position_embeddings)
         self.max_blocks = (self.max_model_len + KV_BLOCK - 1) // KV_BLOCK
@@ -858,10 +863,12 @@ def bench_decode_throughput(args, rank, world):
           "deepseek_r1_distill_70b": "deepseek-ai/DeepSeek-R1-Distill-Llama-70B"}[name]
     return {
         "metric": (f"{label} output tokens/sec (fp8 e4m3 weights, bf16 activations, continuous batching)"
-                   if quant == "fp8" else f"{label} output tokens/sec (bf16, continuous batching)"),
+                   if quant == "fp8" else
+                   f"{label} output tokens/sec (MXFP4 weights, bf16 activations, continuous batching)"
+                   if quant == "mxfp4" else f"{label} output tokens/sec (bf16, continuous batching)"),
         "value": round(toks / el, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(1000 * el / args.steps, 2), "higher_is_better": True,
-        "scaling": "strong" if replicas == 1 else "weak", "vs_baseline": None, "dtype": "fp8w-bf16a" if quant == "fp8" else "bf16",
+        "scaling": "strong" if replicas == 1 else "weak", "vs_baseline": None, "dtype": {"fp8": "fp8w-bf16a", "mxfp4": "mxfp4w-bf16a"}.get(quant, "bf16"),
         "data": "synthetic prompts, random-init weights",
         "config": {"model": f"{hf} (architecture)", "global_batch": B * replicas,
                    "seq_len": P + G, "prompt_len": P, "gen_len": G,

@@ -251,6 +251,8 @@ class LlamaForCausalLM(nn.Module):
         def fold(lin_w, norm):
             if lin_w.dtype == torch.float8_e4m3fn:
                 raise RuntimeError("fold_norms after fp8 quantisation: fold first, then quantize_fp8_")
+            if lin_w.dtype == torch.float4_e2m1fn_x2:
+                raise RuntimeError("fold_norms after MXFP4 quantisation: fold first, then quantize_mxfp4_")
             lin_w.copy_((lin_w.float() * norm.weight.float()[None, :]).to(lin_w.dtype))
             norm.weight.fill_(1.0)
         for layer in self.layers:

@@ -18,13 +18,13 @@ import torch
 
 from .. import native
 from . import reference as ref
-from .reference import (ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, act_id,
-                        pack_conv_weight, pack_up2_phase_weight, unpack_conv_weight)
+from .reference import (ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, act_id, mxfp4_pack,
+                        mxfp4_unpack, quantize_mxfp4, pack_conv_weight, pack_up2_phase_weight, unpack_conv_weight)
 
 __all__ = [
     "rmsnorm", "layernorm", "groupnorm_stats", "groupnorm_apply", "groupnorm", "linear", "conv2d", "attention",
     "paged_attention", "decode_attention", "kv_write", "rope", "rope_pairs", "gated_act", "bias_act", "sched_step",
-    "softmax_", "embedding", "token_feedback", "decode_attention_rope", "decode_attention_rope_qkv", "gemm_partials", "quantize_fp8_rows", "dequant_fp8", "quant_rows_fp8", "gemm_f8", "pack_conv_weight", "pack_up2_phase_weight", "linear_wslices", "unpack_conv_weight", "act_id", "ACT_NONE", "ACT_SILU", "ACT_GELU",
+    "softmax_", "embedding", "token_feedback", "decode_attention_rope", "decode_attention_rope_qkv", "gemm_partials", "quantize_fp8_rows", "dequant_fp8", "quantize_mxfp4", "dequant_mxfp4", "mxfp4_pack", "mxfp4_unpack", "is_mxfp4", "quant_rows_fp8", "gemm_f8", "pack_conv_weight", "pack_up2_phase_weight", "linear_wslices", "unpack_conv_weight", "act_id", "ACT_NONE", "ACT_SILU", "ACT_GELU",
     "ACT_GELU_TANH", "ACT_QUICK_GELU", "ACT_RELU", "decode_splits", "set_decode_wb",
 ]
 
@@ -153,6 +153,36 @@ def dequant_fp8(w8: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> 
     return out
 
 
+# ---- MXFP4 weight-only quantisation (``quantize_mxfp4``: a load-time transform in pure torch, CPU and GPU; format and
+# layout in ops/reference.py).  Decode-shaped GEMMs stream the packed codes (csrc/kernels/gemv_fp4.hip); anything else
+# dequantises to bf16 first (as FP8_PREFILL="dequant" does) -- a fused MX-scaled MFMA prefill GEMM is the follow-up.
+def is_mxfp4(w: torch.Tensor) -> bool:
+    return w.dtype == torch.float4_e2m1fn_x2
+
+
+def dequant_mxfp4(wq: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """MXFP4 codes [N, K / 2] + group scales -> [N, K] (torch on the CPU, the native kernel on the GPU)."""
+    if not wq.is_cuda:
+        return ref.dequant_mxfp4(wq, scales, dtype)
+    out = torch.empty(wq.shape[0], wq.shape[1] * 2, dtype=torch.bfloat16, device=wq.device)
+    _K().dequant_mxfp4(wq, scales, out)
+    return out if dtype == torch.bfloat16 else out.to(dtype)
+
+
+def _mxfp4_route(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor], direct_ok: bool = True):
+    """(w, w_scale) for a GEMM of ``x`` against MXFP4 weights: the packed pair where the fp4 skinny kernel takes the
+    problem (GPU, <= 64 rows, K % 32 == 0), else the dequantised bf16 matrix."""
+    if w_scale is None:
+        raise ValueError("MXFP4 weights need w_scale= (the group scales of quantize_mxfp4)")
+    K = x.shape[-1]
+    if w.shape[1] * 2 != K:
+        raise ValueError(f"MXFP4 weight {tuple(w.shape)} holds K = {w.shape[1] * 2}, the activation has K = {K}")
+    M = x.numel() // K
+    if direct_ok and _gpu(x) and 1 <= M <= 64 and K % 32 == 0:
+        return w, w_scale
+    return dequant_mxfp4(w, w_scale), None
+
+
 # fp8 weights on problems of more than 64 rows (prefill): "w8a8" quantises the activation per row on the fly and
 # runs the fp8 MFMA GEMM (gemm_f8.hip); "dequant" widens the weights to bf16 and runs the bf16 GEMMs
 FP8_PREFILL = os.environ.get("SHAI_FP8_PREFILL", "w8a8")
@@ -203,8 +233,12 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     problems (<= 64 rows) stream the fp8 bytes through the skinny kernel (half the weight
     traffic); larger ones run W8A8 on the fp8 MFMA (``FP8_PREFILL``: the activation is quantised per row, with
     the folded RMSNorm in its row scale) or dequantize to bf16 first and run the bf16 GEMMs.
+    ``w`` of dtype float4_e2m1fn_x2 is MXFP4 (``quantize_mxfp4``; ``w_scale`` its e8m0 group scales): <= 64 rows on
+    the GPU stream the packed codes through the fp4 skinny kernel, everything else dequantises to bf16 first.
     """
-    if w_scale is not None:
+    if is_mxfp4(w):
+        w, w_scale = _mxfp4_route(x, w, w_scale, direct_ok=row_affine is None)
+    if w_scale is not None and not is_mxfp4(w):
         M = x.numel() // x.shape[-1]
         K = x.shape[-1]
         if (_gpu(x) and M > 64 and FP8_PREFILL == "w8a8" and alpha == 1.0 and K % 16 == 0
@@ -234,8 +268,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     Nout = N // 2 if glu else N
     y = torch.empty(x2.shape[0], Nout, dtype=x.dtype, device=x.device)
     r2 = residual.reshape(-1, Nout) if residual is not None else None
-    _K().gemm(x2, w, y, bias, None, 1, r2, float(alpha), float(res_alpha), act_id(act), bool(glu), None, 1, -1,
-              float(rms_eps) if rms_eps is not None else -1.0, w_scale)
+    _K().gemm(x2, w, y, bias, None, 1, r2, float(alpha), float(res_alpha), act_id(act), bool(glu), None, 1,
+              int(force_cfg) if is_mxfp4(w) else -1, float(rms_eps) if rms_eps is not None else -1.0, w_scale)
     return y.view(*lead, Nout)
 
 
@@ -388,13 +422,19 @@ def gemm_into(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias=None, ac
               force_cfg: int = -1, rms_eps: float = -1.0, w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = gate[row // rows_per_gate] * act(alpha * x @ w^T + bias) + res_alpha * residual, written into ``out``.
     rms_eps >= 0: x is RMS-normalised first (unweighted; fold the gain into w).
-    w_scale: fp8 e4m3 ``w`` with per-row scales (skinny kernel only, as in ``linear``).
+    w_scale: fp8 e4m3 ``w`` with per-row scales (skinny kernel only, as in ``linear``), or the group scales of an
+    MXFP4 ``w`` (2-D x of <= 64 rows without a gate: the fp4 skinny kernel, force_cfg 1000 (+ kg) / 1100 + kg as
+    below; anything else dequantises first).
     force_cfg (tests / tools): a tile config index, 1000 (+ kg) = skinny kernel with a separate split-K fold,
     1100 + kg = skinny kernel reducing its K groups inside the launch, 2000 = hipBLASLt.
 
     x / out / residual are 2D [M, *] or 3D [B, M, *] views whose rows may be strided
     (e.g. the text / image halves of a joint-sequence buffer); the row index used
     for ``gate`` is the flattened b * M + m (AdaLN-Zero gates per image)."""
+    if is_mxfp4(w):
+        w, w_scale = _mxfp4_route(x, w, w_scale, direct_ok=x.dim() == 2 and gate is None)
+        if w_scale is None and force_cfg >= 1000:
+            force_cfg = -1  # the forced number named the fp4 kernel
     if not _gpu(x):
         if w_scale is not None:
             w = dequant_fp8(w, w_scale)

@@ -141,6 +141,72 @@ def linear(x, w, bias=None, act=None, residual=None, glu=False, alpha=1.0, res_a
     return y.to(x.dtype)
 
 
+# ---- MXFP4 (OCP microscaling fp4): e2m1 codes, two per byte (even k in the low nibble), one e8m0 scale byte
+# (2^(byte - 127)) per 32 consecutive k of a row.  Logical shapes: codes [N, K / 2], scales [N, K / 32].  The layout the
+# kernels stream (csrc/kernels/gemv_fp4.hip) keeps the codes row-major and tiles the scales per 128-wide K step:
+# [ceil(K / 128), N, 4] bytes, groups past K / 32 padded with 127 (= 1.0).
+MXFP4_GROUP = 32
+MXFP4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def mxfp4_pack(codes: torch.Tensor, scale_bytes: torch.Tensor):
+    """Layout helper: packed codes uint8 [N, K / 2] + scale bytes uint8 [N, K / 32] (logical layout) ->
+    (wq float4_e2m1fn_x2 [N, K / 2], scales float8_e8m0fnu [ceil(K / 128), N, 4]) as the kernels read them."""
+    N, K2 = codes.shape
+    G = scale_bytes.shape[1]
+    assert codes.dtype == torch.uint8 and scale_bytes.dtype == torch.uint8 and scale_bytes.shape[0] == N
+    assert K2 * 2 == G * MXFP4_GROUP, "one scale per 32 codes"
+    steps = (G + 3) // 4
+    sb = torch.full((N, steps * 4), 127, dtype=torch.uint8, device=codes.device)
+    sb[:, :G] = scale_bytes
+    tiled = sb.view(N, steps, 4).permute(1, 0, 2).contiguous()
+    return codes.contiguous().view(torch.float4_e2m1fn_x2), tiled.view(torch.float8_e8m0fnu)
+
+
+def mxfp4_unpack(wq: torch.Tensor, scales: torch.Tensor):
+    """Inverse of ``mxfp4_pack``: (codes uint8 [N, K / 2], scale bytes uint8 [N, K / 32])."""
+    codes = wq.view(torch.uint8)
+    N, K2 = codes.shape
+    G = K2 * 2 // MXFP4_GROUP
+    sb = scales.view(torch.uint8)
+    assert sb.dim() == 3 and sb.shape[1] == N and sb.shape[2] == 4 and sb.shape[0] == (G + 3) // 4, \
+        f"mxfp4 scales {tuple(sb.shape)} do not belong to codes {tuple(codes.shape)}"
+    return codes, sb.permute(1, 0, 2).reshape(N, -1)[:, :G]
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """OCP MX quantisation of w [N, K] (K % 32 == 0) along K: per group of 32, e = floor(log2(amax)) - 2 clamped so
+    that 0.5 * 2^e is a normal bf16, elements / 2^e clamped to +-6 and rounded to the nearest e2m1 value, ties to
+    the even mantissa.  A dequantised weight code * 2^e is exact in bf16.  Returns ``mxfp4_pack``'s pair."""
+    assert w.dim() == 2 and w.shape[1] % MXFP4_GROUP == 0 and w.shape[1] > 0, "quantize_mxfp4: w must be [N, K], K % 32 == 0"
+    N, K = w.shape
+    wf = w.float().reshape(N, K // MXFP4_GROUP, MXFP4_GROUP)
+    amax = wf.abs().amax(dim=-1)
+    _, ex = torch.frexp(amax)                       # amax = m * 2^ex, m in [0.5, 1): floor(log2 amax) = ex - 1
+    e = (ex.to(torch.int32) - 3).clamp(-125, 125)   # an all-zero group: ex = 0, e = -3 (any valid scale), codes 0
+    v = torch.ldexp(wf, -e[..., None]).clamp(-6.0, 6.0)
+    a = v.abs()
+    # nearest of {0, .5, 1, 1.5, 2, 3, 4, 6}; a midpoint goes to the neighbour with the even mantissa (codes 0, 2, 4, 6)
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8)
+            + (a >= 1.75).to(torch.uint8) + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8)
+            + (a > 5.0).to(torch.uint8))
+    code = code | (((v < 0) & (code > 0)).to(torch.uint8) << 3)
+    code = code.reshape(N, K)
+    packed = code[:, 0::2] | (code[:, 1::2] << 4)
+    return mxfp4_pack(packed, (e + 127).to(torch.uint8))
+
+
+def dequant_mxfp4(wq: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """Table decode of ``quantize_mxfp4``'s pair -> [N, K] (exact in bf16 / fp32)."""
+    codes, sb = mxfp4_unpack(wq, scales)
+    N, K2 = codes.shape
+    table = torch.tensor(MXFP4_VALUES + tuple(-x for x in MXFP4_VALUES), dtype=torch.float32, device=codes.device)
+    vals = torch.stack([table[(codes & 15).long()], table[(codes >> 4).long()]], dim=-1).reshape(N, K2 * 2)
+    e = sb.to(torch.int32) - 127
+    out = torch.ldexp(vals.view(N, -1, MXFP4_GROUP), e[..., None]).reshape(N, K2 * 2)
+    return out.to(dtype)
+
+
 def gate_rows(y, gate, rows_per_gate):
     """y [..., M, N] * gate[(b*M + m) // rows_per_gate] (flattened row index)."""
     N = y.shape[-1]

@@ -42,14 +42,39 @@ class _ShardLoadMixin:
     # OCP e4m3 [N, K] + an fp32 per-row ``weight_scale``; decode GEMMs stream half the bytes.
     def quantize_fp8_(self) -> None:
         if getattr(self, "weight_scale", None) is not None:
+            if ops.is_mxfp4(self.weight):
+                raise RuntimeError("quantize_fp8_: the layer already holds MXFP4 weights")
             return
         w8, scale = ops.quantize_fp8_rows(self.weight.data)
         self.weight = nn.Parameter(w8, requires_grad=False)
         self.register_buffer("weight_scale", scale)
 
+    # ---- MXFP4 weight-only quantisation (``quantization: mxfp4``): the weight becomes packed e2m1 codes
+    # [N, K / 2] + e8m0 group scales (``ops.quantize_mxfp4``), quantised AFTER sharding (a group of 32 never
+    # straddles two ranks); decode GEMMs stream a quarter of the bf16 bytes, larger ones dequantise first.
+    def quantize_mxfp4_(self) -> None:
+        if getattr(self, "weight_scale", None) is not None:
+            if not ops.is_mxfp4(self.weight):
+                raise RuntimeError("quantize_mxfp4_: the layer already holds fp8 weights")
+            return
+        k = self.weight.shape[1]
+        if k % 32 != 0:
+            what = (f"row-parallel shard in_local = {k} (in_features {self.in_features} over {self.tp_size} ranks)"
+                    if isinstance(self, RowParallelLinear) else f"in_features = {k}")
+            raise ValueError(f"quantize_mxfp4_: {type(self).__name__} {what} is not a multiple of the MXFP4 group "
+                             "size 32")
+        wq, scales = ops.quantize_mxfp4(self.weight.data)
+        self.weight = nn.Parameter(wq, requires_grad=False)
+        self.register_buffer("weight_scale", scales)
+
     @property
     def w_scale(self):
         return getattr(self, "weight_scale", None)
+
+    @property
+    def _w_cols(self) -> int:
+        """K of this shard's weight (an MXFP4 weight packs two codes per element)."""
+        return self.weight.shape[1] * (2 if ops.is_mxfp4(self.weight) else 1)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         for name, p in list(self._parameters.items()):
@@ -150,7 +175,7 @@ class QKVParallelLinear(_ShardLoadMixin, nn.Module):
 
     def full_shape(self, name):
         n = (self.heads + 2 * self.kv_heads) * self.head_dim
-        return (n, self.weight.shape[1]) if name == "weight" else (n,)
+        return (n, self._w_cols) if name == "weight" else (n,)
 
     def forward(self, x, rms_eps=None):
         return ops.linear(x, self.weight, self.bias, rms_eps=rms_eps, w_scale=self.w_scale)
@@ -174,7 +199,7 @@ class GLUParallelLinear(_ShardLoadMixin, nn.Module):
 
     def full_shape(self, name):
         n = 2 * self.i_local * self.tp_size
-        return (n, self.weight.shape[1]) if name == "weight" else (n,)
+        return (n, self._w_cols) if name == "weight" else (n,)
 
     def forward(self, x, rms_eps=None):
         return ops.linear(x, self.weight, self.bias, act=self.act, glu=True, rms_eps=rms_eps, w_scale=self.w_scale)
@@ -235,5 +260,22 @@ def quantize_fp8_(model: nn.Module) -> int:
     for m in model.modules():
         if isinstance(m, FP8_LAYER_TYPES) and id(m) not in skip:
             m.quantize_fp8_()
+            n += 1
+    return n
+
+
+@torch.no_grad()
+def quantize_mxfp4_(model: nn.Module) -> int:
+    """Quantise every TP linear layer of ``model`` to MXFP4 weights in place: the layer types and the ``no_fp8``
+    opt-out of ``quantize_fp8_`` (embeddings / LM head stay bf16).  Call after any weight transform (RMSNorm gain
+    folding) and after sharding.  Returns the number of layers visited (already-quantised ones are left alone)."""
+    n = 0
+    skip = set()
+    for m in model.modules():
+        if getattr(m, "no_fp8", False):
+            skip.update(id(c) for c in m.modules())
+    for m in model.modules():
+        if isinstance(m, FP8_LAYER_TYPES) and id(m) not in skip:
+            m.quantize_mxfp4_()
             n += 1
     return n

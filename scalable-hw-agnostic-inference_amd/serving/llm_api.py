@@ -13,7 +13,9 @@ greedy).  Unlike vllm_model_api.py:38-43, ``max_new_tokens`` is honoured (the _m
 variant's behaviour).  Engine kwargs come from a /vllm_config.yaml-style file
 (``VLLM_CONFIG``): tensor_parallel_size, max_num_seqs, max_model_len, block_size
 (rounded to 64-token KV blocks), quantization (``fp8``: e4m3 weights + per-row
-scales, bf16 activations).
+scales, bf16 activations; ``mxfp4``: OCP MXFP4 weights -- e2m1 codes with one
+e8m0 scale per 32 inputs, quantised on load -- bf16 activations: the 4-bit
+deployment of the reference's bitsandbytes ``load_in_4bit`` models).
 
 Tensor parallelism (``tensor_parallel_size: N``, app/vllm_model_api.py:127-129 with
 cova/mllama-32-11b-vllm-trn1-config.yaml:9): the worker runs as N processes, one

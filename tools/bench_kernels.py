@@ -150,6 +150,59 @@ def bench_decode_fp8(rows):
                              bf16_TBps=gb / best["bf16"][0] / 1e3, fp8_eqTBps=gb / best["fp8"][0] / 1e3))
 
 
+def bench_fp4(rows):
+    """Decode GEMMs of Mistral-7B and a 70B Llama at M = 1 / 16 / 64 with bf16, fp8 (e4m3 + row scales) and MXFP4
+    weights: the tuned ``ops.linear`` of each (replayed from a HIP graph), the three variants alternating inside
+    every repeat, as the median time, the spread of the repeats ((max - min) / median) and the weight bytes actually streamed over the time.
+    Every variant rotates over enough weight copies to exceed the 256 MB Infinity Cache."""
+    reps = int(os.environ.get("SHAI_FP4_REPS", "5"))
+    shapes = [(6144, 4096), (4096, 4096), (28672, 4096), (4096, 14336), (10240, 8192), (57344, 8192), (8192, 28672)]
+    only = os.environ.get("SHAI_FP4_SHAPES")
+    if only:
+        shapes = [shapes[int(i)] for i in only.split(",")]
+    for N, K in shapes:
+        nbytes = {"bf16": N * K * 2, "fp8": N * K + N * 4, "fp4": N * K // 2 + N * K // 32}
+        ncopy = {v: max(2, min(160, (768 << 20) // b + 1)) for v, b in nbytes.items()}
+        wts = {"bf16": [], "fp8": [], "fp4": []}
+        for i in range(max(ncopy.values())):
+            w = rnd(N, K) * 0.02
+            if i < ncopy["bf16"]:
+                wts["bf16"].append((w, None))
+            if i < ncopy["fp8"]:
+                wts["fp8"].append(ops.quantize_fp8_rows(w))
+            if i < ncopy["fp4"]:
+                wts["fp4"].append(ops.quantize_mxfp4(w))
+            del w
+        for M in (1, 16, 64):
+            a = rnd(M, K)
+            it = {v: 0 for v in wts}
+
+            def run(v):
+                it[v] = (it[v] + 1) % ncopy[v]
+                w, sc = wts[v][it[v]]
+                return ops.linear(a, w, w_scale=sc)
+            for v in wts:   # tune outside the timing
+                run(v)
+            # device time with the host out of the loop (a 4096 x 4096 fp4 GEMM is shorter than one eager launch):
+            # a HIP graph of one pass over the variant's weight copies (at least 32 calls) per measurement
+            ts = {v: [] for v in wts}
+            for _ in range(reps):
+                for v in wts:
+                    n_it = ncopy[v] * ((31 + ncopy[v]) // ncopy[v])
+                    ts[v].append(graph_time(lambda: run(v), iters=n_it, reps=2))
+            r = dict(op="decode_fp4", shape=f"{M}x{N}x{K}")
+            for v in wts:
+                t = sorted(ts[v])
+                med = t[len(t) // 2]
+                r[f"{v}_us"] = med * 1e6
+                r[f"{v}_spread_pct"] = 100.0 * (t[-1] - t[0]) / med
+                r[f"{v}_TBps"] = nbytes[v] / med / 1e12
+            r["fp4_vs_fp8"] = r["fp8_us"] / r["fp4_us"]
+            rows.append(r)
+            print("  ".join(f"{k}={x:.2f}" if isinstance(x, float) else f"{k}={x}" for k, x in r.items()), flush=True)
+        del wts
+
+
 def bench_sdgemm(rows):
     """SD2.1 batch-8 (CFG 16) transformer GEMMs: every tile config (forced) vs the tuned choice vs hipBLASLt."""
     shapes = [("sq4096", 4096, 4096, 4096, False), ("sq8192", 8192, 8192, 8192, False),
@@ -329,7 +382,7 @@ def main():
     with torch.inference_mode():
         for name in a.only.split(","):
             {"gemm": bench_gemm, "conv": bench_conv, "attn": bench_attn, "norm": bench_norm,
-             "decode": bench_decode, "decode_fp8": bench_decode_fp8, "sdgemm": bench_sdgemm, "f8": bench_f8,
+             "decode": bench_decode, "decode_fp8": bench_decode_fp8, "fp4": bench_fp4, "sdgemm": bench_sdgemm, "f8": bench_f8,
              "dattn": bench_dattn, "dattn_long": bench_dattn_long}[name](rows)
     for r in rows:
         print("  ".join(f"{k}={v:.1f}" if isinstance(v, float) else f"{k}={v}" for k, v in r.items()), flush=True)
