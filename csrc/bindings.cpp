@@ -7,6 +7,7 @@
 #include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <mutex>
@@ -541,6 +542,33 @@ void check_f32(const Tensor& t, const char* name) {
 void check_i32(const Tensor& t, const char* name) {
   SHAI_CHECK(t.is_cuda() && t.scalar_type() == at::kInt && t.is_contiguous(), name, " must be contiguous int32 GPU");
 }
+// fp8 (OCP e4m3fn) KV cache: both caches fp8, contiguous [blocks, Hkv, 64, D] with D a multiple of 16 (the kernels
+// move 16 codes per 16-byte access), positive finite scales.  Returns false for a bf16 pair (the caller's bf16
+// checks then apply); a mixed pair is an error.
+bool kv8_cache(const Tensor& k_cache, const Tensor& v_cache, double k_scale, double v_scale) {
+  const bool k8 = k_cache.scalar_type() == at::kFloat8_e4m3fn, v8 = v_cache.scalar_type() == at::kFloat8_e4m3fn;
+  SHAI_CHECK(k8 == v8, "k_cache / v_cache dtypes differ (", k_cache.scalar_type(), " vs ", v_cache.scalar_type(),
+             "): an fp8 KV cache needs both as float8_e4m3fn");
+  if (!k8) return false;
+  SHAI_CHECK(k_cache.is_cuda() && v_cache.is_cuda(), "fp8 KV cache must be on the GPU");
+  SHAI_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 64 && v_cache.sizes() == k_cache.sizes(),
+             "fp8 KV cache must be [blocks, Hkv, 64, D]");
+  SHAI_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous(), "fp8 KV cache must be contiguous");
+  SHAI_CHECK(k_cache.size(3) % 16 == 0, "fp8 KV cache needs D % 16 == 0, got D = ", k_cache.size(3));
+  SHAI_CHECK(reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
+                 reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0, "fp8 KV cache must be 16-byte aligned");
+  SHAI_CHECK(k_scale > 0 && v_scale > 0 && std::isfinite(k_scale) && std::isfinite(v_scale),
+             "k_scale / v_scale must be positive and finite");
+  return true;
+}
+uint8_t* u8ptr(const Tensor& t) { return reinterpret_cast<uint8_t*>(t.data_ptr()); }
+void kv8_scales(shai::DecodeAttnArgs& a, double k_scale, double v_scale) {
+  a.k_scale = (float)k_scale;
+  a.v_scale = (float)v_scale;
+  a.k_inv = 1.0f / a.k_scale;  // computed once, in fp32: the quantisation rule's 1 / scale
+  a.v_inv = 1.0f / a.v_scale;
+}
+
 void check_rows(const Tensor& t, const char* name) {
   check_bf16(t, name);
   for (int d = 0; d + 1 < t.dim(); ++d) SHAI_CHECK(t.stride(d) % 8 == 0 || t.size(d) == 1, name, " stride not 16B aligned");
@@ -1306,11 +1334,14 @@ void paged_attn_varlen(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
 
 void decode_attn(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& o,
                  const Tensor& block_table, const Tensor& ctx_lens, const Tensor& ws, int64_t num_splits,
-                 double scale) {
+                 double scale, double k_scale, double v_scale) {
   check_rows(q, "q");
   check_rows(o, "o");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
+  const bool f8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
+  if (!f8) {
+    check_bf16(k_cache, "k_cache");
+    check_bf16(v_cache, "v_cache");
+  }
   check_i32(block_table, "block_table");
   check_i32(ctx_lens, "ctx_lens");
   check_f32(ws, "ws");
@@ -1336,6 +1367,12 @@ void decode_attn(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, 
   a.q_bs = q.stride(0);
   a.o_bs = o.stride(0);
   a.scale = scale;
+  if (f8) {
+    SHAI_CHECK(k_cache.size(3) == a.D, "decode_attn: cache head dim != q head dim");
+    kv8_scales(a, k_scale, v_scale);
+    shai::launch_decode_attn_kv8(a, stream());
+    return;
+  }
   shai::launch_decode_attn(a, stream());
 }
 
@@ -1384,12 +1421,15 @@ void decode_attn_rope(const Tensor& qkv, const Tensor& k_cache, const Tensor& v_
                       const Tensor& block_table, const Tensor& ctx_lens, const Tensor& positions, const Tensor& cos,
                       const Tensor& sin, const Tensor& slots, const Tensor& ws, int64_t h, int64_t hk,
                       int64_t num_splits, double scale, const optional<Tensor>& qkv_ws, int64_t qkv_kg,
-                      int64_t qkv_k, double qkv_eps) {
+                      int64_t qkv_k, double qkv_eps, double k_scale, double v_scale) {
   const bool part = qkv_ws.has_value();
   if (!part) check_bf16(qkv, "qkv");  // partials path: qkv is a placeholder (the partials), never read
   check_rows(o, "o");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
+  const bool f8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
+  if (!f8) {
+    check_bf16(k_cache, "k_cache");
+    check_bf16(v_cache, "v_cache");
+  }
   check_i32(block_table, "block_table");
   check_i32(ctx_lens, "ctx_lens");
   check_i32(positions, "positions");
@@ -1449,15 +1489,31 @@ void decode_attn_rope(const Tensor& qkv, const Tensor& k_cache, const Tensor& v_
   a.ws = ws.data_ptr<float>();
   SHAI_CHECK(ws.numel() * 4 >= (long)shai::decode_attn_workspace(a.B, a.Hq, a.D, num_splits), "ws too small");
   a.scale = scale;
+  if (f8) {
+    kv8_scales(a, k_scale, v_scale);
+    shai::launch_decode_attn_kv8(a, stream());
+    return;
+  }
   shai::launch_decode_attn(a, stream());
 }
 
-void kv_write(const Tensor& k, const Tensor& v, const Tensor& k_cache, const Tensor& v_cache, const Tensor& slots) {
+void kv_write(const Tensor& k, const Tensor& v, const Tensor& k_cache, const Tensor& v_cache, const Tensor& slots,
+              double k_scale, double v_scale) {
   check_rows(k, "k");
   check_rows(v, "v");
+  check_i32(slots, "slots");
+  if (kv8_cache(k_cache, v_cache, k_scale, v_scale)) {
+    SHAI_CHECK(k.dim() == 3 && v.sizes() == k.sizes() && k.size(1) == k_cache.size(1) && k.size(2) == k_cache.size(3),
+               "k / v [T, Hkv, D] must match the cache [blocks, Hkv, 64, D]");
+    SHAI_CHECK(k.stride(1) == k.size(2) && v.stride(1) == v.size(2), "packed heads");
+    SHAI_CHECK(slots.numel() == k.size(0), "slots must have T entries");
+    shai::launch_kv_write_f8(cptr(k), cptr(v), u8ptr(k_cache), u8ptr(v_cache), slots.data_ptr<int>(), k.size(0),
+                             k.size(1), k.size(2), k.stride(0), v.stride(0), 1.0f / (float)k_scale,
+                             1.0f / (float)v_scale, stream());
+    return;
+  }
   check_bf16(k_cache, "k_cache");
   check_bf16(v_cache, "v_cache");
-  check_i32(slots, "slots");
   SHAI_CHECK(k.dim() == 3 && k_cache.dim() == 4, "k [T, Hkv, D], cache [blocks, Hkv, 64, D]");
   SHAI_CHECK(k.stride(1) == k.size(2) && v.stride(1) == v.size(2), "packed heads");
   shai::launch_kv_write(cptr(k), cptr(v), mptr(k_cache), mptr(v_cache), slots.data_ptr<int>(), k.size(0), k.size(1),
@@ -1508,10 +1564,14 @@ void rope(const Tensor& x, const Tensor& positions, const Tensor& cos, const Ten
 }
 
 void rope_qkv_cache(const Tensor& qkv, const Tensor& positions, const Tensor& cos, const Tensor& sin,
-                    const Tensor& k_cache, const Tensor& v_cache, const Tensor& slots, int64_t H, int64_t Hkv) {
+                    const Tensor& k_cache, const Tensor& v_cache, const Tensor& slots, int64_t H, int64_t Hkv,
+                    double k_scale, double v_scale) {
   check_bf16(qkv, "qkv");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
+  const bool f8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
+  if (!f8) {
+    check_bf16(k_cache, "k_cache");
+    check_bf16(v_cache, "v_cache");
+  }
   check_i32(positions, "positions");
   check_i32(slots, "slots");
   check_f32(cos, "cos");
@@ -1525,9 +1585,34 @@ void rope_qkv_cache(const Tensor& qkv, const Tensor& positions, const Tensor& co
   SHAI_CHECK(cos.size(-1) == D / 2, "cos/sin must be [max_pos, D/2] (full-dim NeoX rotation)");
   const int T = qkv.size(0);
   SHAI_CHECK(positions.numel() == T && slots.numel() == T, "positions / slots must have T entries");
+  if (f8) {
+    shai::launch_rope_qkv_cache_f8(mptr(qkv), qkv.stride(0), positions.data_ptr<int>(), cos.data_ptr<float>(),
+                                   sin.data_ptr<float>(), u8ptr(k_cache), u8ptr(v_cache), slots.data_ptr<int>(), T, H,
+                                   Hkv, D, 1.0f / (float)k_scale, 1.0f / (float)v_scale, stream());
+    return;
+  }
   shai::launch_rope_qkv_cache(mptr(qkv), qkv.stride(0), positions.data_ptr<int>(), cos.data_ptr<float>(),
                               sin.data_ptr<float>(), mptr(k_cache), mptr(v_cache), slots.data_ptr<int>(), T, H, Hkv,
                               D, stream());
+}
+
+// Widen the fp8 cache blocks phys[0 .. n-1] into bf16 scratch blocks 0 .. n-1 (same [., Hkv, 64, D] block layout),
+// value = float(code) * scale: the bf16 prefill attention kernels then run on the scratch with a block table
+// remapped to scratch indices.
+void kv_dequant_blocks(const Tensor& k_cache, const Tensor& v_cache, const Tensor& phys, const Tensor& k_out,
+                       const Tensor& v_out, double k_scale, double v_scale) {
+  SHAI_CHECK(kv8_cache(k_cache, v_cache, k_scale, v_scale), "kv_dequant_blocks: the caches must be float8_e4m3fn");
+  check_bf16(k_out, "k_out");
+  check_bf16(v_out, "v_out");
+  check_i32(phys, "phys");
+  SHAI_CHECK(k_out.dim() == 4 && k_out.is_contiguous() && v_out.is_contiguous() && v_out.sizes() == k_out.sizes() &&
+                 k_out.size(1) == k_cache.size(1) && k_out.size(2) == 64 && k_out.size(3) == k_cache.size(3),
+             "scratch must be contiguous bf16 [capacity, Hkv, 64, D] matching the cache");
+  SHAI_CHECK(phys.dim() == 1 && phys.numel() <= k_out.size(0), "kv_dequant_blocks: ", phys.numel(),
+             " blocks do not fit the scratch capacity ", k_out.size(0));
+  shai::launch_kv_dequant_blocks(u8ptr(k_cache), u8ptr(v_cache), phys.data_ptr<int>(), (int)phys.numel(),
+                                 k_cache.size(1) * 64 * k_cache.size(3), mptr(k_out), mptr(v_out), (float)k_scale,
+                                 (float)v_scale, stream());
 }
 
 void sample(const Tensor& logits, const Tensor& temps, const Tensor& top_k, const Tensor& top_p,
@@ -1798,14 +1883,15 @@ TORCH_LIBRARY(shai, m) {
   m.def("conv2d(Tensor x, Tensor? x2, Tensor w, Tensor(a!) out, Tensor? bias, Tensor? bias2d, Tensor? residual, Tensor? in_scale, Tensor? in_shift, int in_act, int kh, int kw, int stride, int pad, bool upsample, int act, float res_alpha, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, bool up_phases=False) -> ()");
   m.def("flash_attn(Tensor q, Tensor k, Tensor v, Tensor(a!) o, float scale, bool causal, int causal_offset, Tensor? kv_lens, Tensor? q_lens, Tensor? bias, Tensor? block_table) -> ()");
   m.def("paged_attn_varlen(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor kv_lens, Tensor q_lens, Tensor q_start, int max_q, float scale, bool causal) -> ()");
-  m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor ctx_lens, Tensor(b!) ws, int num_splits, float scale) -> ()");
-  m.def("kv_write(Tensor k, Tensor v, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots) -> ()");
+  m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor ctx_lens, Tensor(b!) ws, int num_splits, float scale, float k_scale=1.0, float v_scale=1.0) -> ()");
+  m.def("kv_write(Tensor k, Tensor v, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots, float k_scale=1.0, float v_scale=1.0) -> ()");
+  m.def("kv_dequant_blocks(Tensor k_cache, Tensor v_cache, Tensor phys, Tensor(a!) k_out, Tensor(b!) v_out, float k_scale, float v_scale) -> ()");
   m.def("gated_act(Tensor x, Tensor(a!) out, int act, bool gate_first) -> ()");
   m.def("bias_act(Tensor x, Tensor? bias, Tensor? residual, Tensor(a!) out, int act, float alpha) -> ()");
   m.def("rope(Tensor(a!) x, Tensor positions, Tensor cos, Tensor sin, int rot_dim, bool neox) -> ()");
   m.def("rope_pairs(Tensor(a!) x, Tensor cos, Tensor sin) -> ()");
   m.def("sample(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out) -> ()");
-  m.def("rope_qkv_cache(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor slots, int H, int Hkv) -> ()");
+  m.def("rope_qkv_cache(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor slots, int H, int Hkv, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("sched_step(Tensor model_out, Tensor(a!) latents, bool cfg, float guidance, int pred_type, float a_t, float a_prev, float dt) -> ()");
   m.def("sched_step_rows(Tensor model_out, Tensor(a!) latents, bool cfg, float guidance, int pred_type, Tensor rows_params) -> ()");
   m.def("softmax_(Tensor(a!) x, float scale) -> ()");
@@ -1813,7 +1899,7 @@ TORCH_LIBRARY(shai, m) {
   m.def("token_feedback(Tensor(a!) ids, Tensor rowmap, Tensor prev) -> ()");
   m.def("decode_attn_rope(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) o, Tensor block_table, "
         "Tensor ctx_lens, Tensor positions, Tensor cos, Tensor sin, Tensor slots, Tensor(d!) ws, int h, int hk, "
-        "int num_splits, float scale, Tensor? qkv_ws=None, int qkv_kg=0, int qkv_k=0, float qkv_eps=-1.0) -> ()");
+        "int num_splits, float scale, Tensor? qkv_ws=None, int qkv_kg=0, int qkv_k=0, float qkv_eps=-1.0, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("gemm_partials(Tensor a, Tensor w, float rms_eps) -> Tensor");
   m.def("gemm_lnout(Tensor a, Tensor w, Tensor(a!) c, Tensor(b!) c2, Tensor? bias, Tensor residual, float res_alpha, Tensor? gamma, Tensor? beta, float eps) -> bool");
   m.def("gemm_tuning() -> str[]", &gemm_tuning);
@@ -1845,6 +1931,7 @@ TORCH_LIBRARY_IMPL(shai, CUDA, m) {
   m.impl("paged_attn_varlen", &paged_attn_varlen);
   m.impl("decode_attn", &decode_attn);
   m.impl("kv_write", &kv_write);
+  m.impl("kv_dequant_blocks", &kv_dequant_blocks);
   m.impl("gated_act", &gated_act);
   m.impl("bias_act", &bias_act);
   m.impl("rope", &rope);

@@ -39,7 +39,10 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 KERNEL_SRCS = ["kernels/norm.hip", "kernels/gemm.hip", "kernels/gemm_lds.hip", "kernels/gemm_8ph.hip", "kernels/gemm_w4.hip", "kernels/gemm_ws.hip", "kernels/conv_halo.hip", "kernels/attention.hip", "kernels/attention2.hip", "kernels/attention3.hip", "kernels/elementwise.hip", "kernels/dit.hip",
                "kernels/sampling.hip", "kernels/gemv.hip", "kernels/gemv2.hip", "kernels/gemv_fp4.hip",
-               "kernels/gemm_f8.hip"]
+               "kernels/gemm_f8.hip", "kernels/attention_kv8.hip"]
+# sources whose kernels must not spill: compiled with the resource-usage remarks on, and build() fails when any of
+# their kernels reports scratch (the hand-scheduled fp8-cache decode kernel sits near its register budget)
+NO_SCRATCH_SRCS = ["kernels/attention_kv8.hip"]
 # per-source extra hipcc flags: gemm_w4's epilogue (256 accumulators x an activation) is larger than LLVM's
 # default pragma-unroll budget; partially unrolled it would index the accumulators at run time (scratch)
 EXTRA_KFLAGS = {"kernels/attention3.hip": "-mllvm -amdgpu-mfma-vgpr-form -fno-slp-vectorize",
@@ -115,8 +118,11 @@ def write_ninja(path: str, out: str = OUT, build_dir: str = BUILD, debug: bool =
             o = os.path.join(build_dir, s.replace("/", "_") + ".o")
             lines.append(f"build {o}: {rule} {os.path.join(CSRC, s)} | {os.path.join(CSRC, 'kernels', 'common.h')} "
                          f"{os.path.join(CSRC, 'kernels', 'launchers.h')}")
-            if s in EXTRA_KFLAGS:
-                lines.append(f"  kflags = $kflags {EXTRA_KFLAGS[s]}")
+            extra = EXTRA_KFLAGS.get(s, "")
+            if s in NO_SCRATCH_SRCS:
+                extra = (extra + " -Rpass-analysis=kernel-resource-usage").strip()
+            if extra:
+                lines.append(f"  kflags = $kflags {extra}")
             out.append(o)
         return out
 
@@ -140,6 +146,23 @@ def write_ninja(path: str, out: str = OUT, build_dir: str = BUILD, debug: bool =
 LAST_BUILD: dict = {}
 
 
+def check_no_scratch(log: str) -> None:
+    """Fail the build when a kernel of NO_SCRATCH_SRCS spills: its compile prints one 'Function Name' and one
+    'ScratchSize [bytes/lane]' remark per kernel (only when the object was recompiled; a reused object passed
+    this check when it was built)."""
+    names = tuple(os.path.basename(s) for s in NO_SCRATCH_SRCS)
+    fn, bad = "?", []
+    for ln in log.splitlines():
+        if not any(n in ln for n in names):
+            continue
+        if "Function Name:" in ln:
+            fn = ln.split("Function Name:", 1)[1].split()[0]
+        elif "ScratchSize [bytes/lane]:" in ln and int(ln.split("ScratchSize [bytes/lane]:", 1)[1].split()[0]) > 0:
+            bad.append(f"{fn}: {ln.split('ScratchSize [bytes/lane]:', 1)[1].split()[0]} bytes/lane")
+    if bad:
+        raise RuntimeError("kernels that must not use scratch memory spill: " + "; ".join(bad))
+
+
 def build(clean: bool = False, jobs: int | None = None, verbose: bool = False, debug: bool = False) -> dict:
     out, bdir = (OUT_DEBUG, BUILD_DEBUG) if debug else (OUT, BUILD)
     if clean and os.path.isdir(bdir):
@@ -158,9 +181,12 @@ def build(clean: bool = False, jobs: int | None = None, verbose: bool = False, d
     if verbose:
         cmd.append("-v")
     r = subprocess.run(cmd, cwd=bdir, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    sys.stdout.write(r.stdout)
+    # (the resource-usage remarks of NO_SCRATCH_SRCS are read by check_no_scratch below, not printed)
+    sys.stdout.write("".join(ln for ln in r.stdout.splitlines(True) if "[-Rpass-analysis=" not in ln))
     if r.returncode != 0:
         raise subprocess.CalledProcessError(r.returncode, cmd, r.stdout)
+    if not debug:   # (the debug flavour's device asserts call printf, which takes scratch by itself)
+        check_no_scratch(r.stdout)
     # what ninja actually did: "[i/n] HIP <src>" per compiled object, "no work to do" when all were reused
     compiled = [ln.split("] ", 1)[1].split(" ", 1)[1] for ln in r.stdout.splitlines()
                 if ln.startswith("[") and ("] HIP " in ln or "] CXX " in ln)]

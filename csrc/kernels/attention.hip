@@ -18,6 +18,7 @@
 //   split-K over 64-token blocks (memory-bound; VALU dot products, K/V
 //   staged through LDS), followed by a split combine.
 #include "common.h"
+#include "decode_common.h"
 #include "launchers.h"
 
 #include <algorithm>
@@ -589,13 +590,7 @@ typedef __bf16 bf16x8d __attribute__((ext_vector_type(8)));
 // instructions per wave per block + one barrier), so HBM latency hides behind the dot products.
 // Per-block buffer descriptors (the cache can exceed 4 GiB) range-check the tail rows past the
 // context: zero-filled, since P = 0 times a never-written NaN pattern would poison P.V.
-// Split count of one sequence of nblk 64-token blocks when the launch has num_splits: at least kDaMinSplitBlocks
-// blocks per split, so that a batch whose factor was raised for one long context (up to 64 splits at 128k) does
-// not give every short sequence 64 mostly-empty workgroups and a 64-way combine.
-constexpr int kDaMinSplitBlocks = 4;
-__device__ __forceinline__ int da_splits(int nblk, int num_splits) {
-  return max(1, min(num_splits, (nblk + kDaMinSplitBlocks - 1) / kDaMinSplitBlocks));
-}
+// (da_splits, the per-sequence split count, lives in decode_common.h: the fp8-cache kernel shares it)
 
 template <int D, int NI>
 __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* dsm, const int b, const int hk,
@@ -1217,6 +1212,11 @@ __global__ void __launch_bounds__(kWbG * 64, 2) decode_attn_wb_kernel(const Deco
   }
   const float inv = L > 0.f ? 1.f / L : 0.f;
   *reinterpret_cast<uint32_t*>(p.o + (long)b * p.o_bs + (long)hq * D + 2 * lane) = pack2(o0 * inv, o1 * inv);
+}
+
+// the split combine for launchers in other translation units (attention_kv8.hip: same partial format)
+void launch_decode_combine(const DecodeAttnArgs& a, hipStream_t s) {
+  decode_combine_kernel<<<dim3(a.B, a.Hq), 128, 0, s>>>(a);
 }
 
 static int g_decode_wb = -1;

@@ -304,8 +304,25 @@ struct DecodeAttnArgs {
   const float* qkv_ws;
   int qkv_kg, qkv_n, qkv_k;
   float qkv_eps;
+  // fp8 (OCP e4m3fn) cache (launch_decode_attn_kv8 only; k_cache / v_cache then point at bytes): stored code =
+  // fp8(clamp(x * k_inv, +-448)), value = float(code) * k_scale; k_inv = 1 / k_scale computed on the host
+  float k_scale, v_scale, k_inv, v_inv;
 };
 void launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
+// the split combine alone (partials ws[b][hq][split] = {m, l, o[D]} -> o), shared by both cache dtypes
+void launch_decode_combine(const DecodeAttnArgs& a, hipStream_t s);
+// fp8 KV cache (attention_kv8.hip): the split decode kernel over byte caches (always the split kernel: there is no
+// wave-per-block form), the cache writers, and the block widener that feeds the bf16 prefill kernels
+void launch_decode_attn_kv8(const DecodeAttnArgs& a, hipStream_t s);
+void launch_kv_write_f8(const bf16_t* k, const bf16_t* v, uint8_t* k_cache, uint8_t* v_cache, const int* slot_mapping,
+                        int T, int Hkv, int D, long k_ts, long v_ts, float k_inv, float v_inv, hipStream_t s);
+void launch_rope_qkv_cache_f8(bf16_t* qkv, long ld, const int* pos, const float* cos, const float* sin,
+                              uint8_t* k_cache, uint8_t* v_cache, const int* slots, int T, int H, int Hkv, int D,
+                              float k_inv, float v_inv, hipStream_t s);
+// scratch block i (bf16, [n, Hkv, 64, D]) = float(fp8 cache block phys[i]) * scale, for K and V
+void launch_kv_dequant_blocks(const uint8_t* k_cache, const uint8_t* v_cache, const int* phys, int n,
+                              long block_elems, bf16_t* k_out, bf16_t* v_out, float k_scale, float v_scale,
+                              hipStream_t s);
 // short-context decode routing (D 128, GQA 4, one split -> the wave-per-block kernel); SHAI_DECODE_WB=0 / mode 0: split kernel
 int decode_wb_mode();
 int set_decode_wb(int mode);   // -1 keeps the mode; returns the previous one

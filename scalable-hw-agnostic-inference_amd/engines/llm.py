@@ -329,16 +329,40 @@ class _Inflight:
         self.seqs, self.toks, self.event, self.cross = seqs, toks, event, cross
 
 
+KV_CACHE_DTYPES = {"auto": torch.bfloat16, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16,
+                   "fp8": torch.float8_e4m3fn, "fp8_e4m3": torch.float8_e4m3fn}
+
+
+def resolve_kv_cache_dtype(kv_cache_dtype: Optional[str]):
+    """vLLM-style ``kv_cache_dtype``: None reads ``SHAI_KV_CACHE_DTYPE`` (unset: auto); auto / bf16 keep the bf16
+    cache, fp8 / fp8_e4m3 select the OCP e4m3fn cache.  Returns (canonical name, torch dtype)."""
+    name = kv_cache_dtype if kv_cache_dtype is not None else os.environ.get("SHAI_KV_CACHE_DTYPE")
+    name = "auto" if name is None or str(name).strip() == "" else str(name).strip().lower()
+    if name not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype={kv_cache_dtype if kv_cache_dtype is not None else name!r}: supported: "
+                         "auto, bf16 (bfloat16 cache) or fp8, fp8_e4m3 (OCP e4m3fn cache with scalar k/v scales)")
+    dt = KV_CACHE_DTYPES[name]
+    return ("fp8" if dt == torch.float8_e4m3fn else "auto"), dt
+
+
 class LLMEngine:
     def __init__(self, cfg: LlamaConfig, device="cuda", model_path: Optional[str] = None, seed: int = 0,
                  max_num_seqs: int = 64, max_model_len: int = 4096, num_kv_blocks: Optional[int] = None,
                  gpu_memory_utilization: float = 0.85, prefill_token_budget: int = 8192, use_graphs: bool = True,
                  enable_prefix_caching: bool = True, prefill_chunk: Optional[int] = None,
                  quantization: Optional[str] = None, async_decode: Optional[bool] = None,
-                 packed_prefill: bool = True, mixed_steps: bool = True):
+                 packed_prefill: bool = True, mixed_steps: bool = True, kv_cache_dtype: Optional[str] = None,
+                 k_scale: float = 1.0, v_scale: float = 1.0, kv_scratch_blocks: Optional[int] = None):
         from ..models.mllama import MllamaConfig, MllamaForConditionalGeneration
         from ..runtime import BlockManager
+        self.kv_cache_dtype, self.kv_dtype = resolve_kv_cache_dtype(kv_cache_dtype)
+        self.kv_fp8 = self.kv_dtype == torch.float8_e4m3fn
         self.mcfg = cfg if isinstance(cfg, MllamaConfig) else None
+        if self.kv_fp8 and self.mcfg is not None:
+            raise NotImplementedError("kv_cache_dtype=fp8 is not supported yet for multimodal (mllama) models: the "
+                                      "image cross-attention K/V path is bf16 only")
+        if self.kv_fp8 and not (k_scale > 0 and v_scale > 0 and math.isfinite(k_scale) and math.isfinite(v_scale)):
+            raise ValueError(f"k_scale / v_scale must be positive and finite, got {k_scale}, {v_scale}")
         if self.mcfg is not None:
             cfg = self.mcfg.text
         self.cfg = cfg
@@ -369,16 +393,38 @@ class LLMEngine:
         self.max_cross_blocks = (self.cross_tokens + KV_BLOCK - 1) // KV_BLOCK
         hk = self.model.kv_heads_local
         per_seq = self.max_blocks + self.max_cross_blocks
+        # fp8 cache: per-layer scalar scales (value = code * scale), the same on every TP rank, and the bf16
+        # scratch the prefill / mixed steps widen blocks into (one layer at a time, reused by every layer).  Its
+        # capacity is fixed here -- at least one full max_model_len sequence plus a block -- and comes out of the
+        # memory budget before the block pool is sized.
+        self.k_scales = [float(k_scale)] * cfg.num_hidden_layers
+        self.v_scales = [float(v_scale)] * cfg.num_hidden_layers
+        self.kv_scratch = None
+        self.kv_scratch_blocks = 0
+        scratch_bytes = 0
+        if self.kv_fp8:
+            self.set_kv_scales(self.k_scales, self.v_scales)
+            want = kv_scratch_blocks if kv_scratch_blocks is not None else max(
+                self.max_blocks + 1, (prefill_token_budget + KV_BLOCK - 1) // KV_BLOCK + max_num_seqs)
+            self.kv_scratch_blocks = max(int(want), self.max_blocks + 1)
+            shape = (2, self.kv_scratch_blocks, hk, KV_BLOCK, cfg.head_dim)
+            scratch_bytes = 2 * self.kv_scratch_blocks * hk * KV_BLOCK * cfg.head_dim * 2
+            buf = torch.empty(shape, dtype=torch.bfloat16, device=self.device)
+            self.kv_scratch = (buf[0], buf[1])
+        self.kv_blocks_budget = None   # blocks the memory budget allows, before the cap by what max_num_seqs can use
         if num_kv_blocks is None:
             if self.device.type == "cuda":
-                free, total = torch.cuda.mem_get_info(self.device)
+                free, total = torch.cuda.mem_get_info(self.device)   # (free already excludes the scratch above)
                 budget = free - (1 - gpu_memory_utilization) * total
-                num_kv_blocks = int(max(budget, 0) // kv_bytes_per_block(cfg, hk))
+                num_kv_blocks = int(max(budget, 0) // kv_bytes_per_block(cfg, hk, self.kv_dtype))
+                self.kv_blocks_budget = num_kv_blocks
                 num_kv_blocks = max(16, min(num_kv_blocks, max_num_seqs * per_seq + 64))
             else:
                 num_kv_blocks = max_num_seqs * per_seq + 8
         self.num_kv_blocks = num_kv_blocks
-        self.kv_buf, self.kv = allocate_kv_cache(cfg, hk, num_kv_blocks, self.device)
+        self.kv_buf, self.kv = allocate_kv_cache(cfg, hk, num_kv_blocks, self.device, dtype=self.kv_dtype)
+        self.kv_bytes = num_kv_blocks * kv_bytes_per_block(cfg, hk, self.kv_dtype)
+        self.kv_scratch_bytes = scratch_bytes
         self.bm = BlockManager(num_kv_blocks)
         self.prefill_token_budget = prefill_token_budget
         # longest prompt slice one prefill step processes (chunked prefill; SURVEY 5.7: <= 8k tokens)
@@ -408,6 +454,24 @@ class LLMEngine:
         self.tok_flip = 0
         self.stats = {"prefill_tokens": 0, "decode_tokens": 0, "steps": 0, "prefix_hit_tokens": 0}
         self.eos = {cfg.eos_token_id}
+
+    def set_kv_scales(self, k_scales: Sequence[float], v_scales: Sequence[float]) -> None:
+        """Per-layer fp8 KV scales (what a checkpoint loader would fill); call before any token is cached and
+        before graph capture -- captured decode graphs hold the values."""
+        layers = self.model.layers
+        if len(k_scales) != len(layers) or len(v_scales) != len(layers):
+            raise ValueError("one k_scale and one v_scale per layer")
+        self.k_scales, self.v_scales = [float(x) for x in k_scales], [float(x) for x in v_scales]
+        for layer, ks, vs in zip(layers, self.k_scales, self.v_scales):
+            layer.self_attn.k_scale, layer.self_attn.v_scale = ks, vs
+
+    def _attach_kv_rounds(self, batch: Batch, bt, lens, qlens, qstart, S: int) -> None:
+        """fp8 cache: plan this prefill step's dequant + attention rounds from the host block lists (no device
+        sync) and hand the scratch to the model."""
+        if not self.kv_fp8 or self.device.type != "cuda":
+            return
+        batch.kv_scratch = self.kv_scratch
+        batch.kv_rounds = ops.build_kv_rounds(bt, lens, qlens, qstart, self.kv_scratch_blocks, self.device, S)
 
     def decode_splits(self, Bc: int, max_ctx: int) -> int:
         """Split-K factor of the decode attention for a batch whose longest context is ``max_ctx`` tokens:
@@ -574,6 +638,7 @@ class LLMEngine:
                                              dtype=np.int32) for s, n in zip(rows, news)])
             batch = Batch(t(ids), t(pos), t(slots), t(bt), t(lens), t(qlens), len(rows), S, True, 1,
                           t(last).long(), q_start=t(qstart))
+            self._attach_kv_rounds(batch, bt, lens, qlens, qstart, S)
         else:
             from ..runtime import build_prefill
             pos, slots, lens, qlens, bt, last = build_prefill([s.n_cached for s in seqs], news,
@@ -582,6 +647,7 @@ class LLMEngine:
             for i, (s, n) in enumerate(zip(seqs, news)):
                 ids[i * S:i * S + n] = s.prompt[s.n_cached:s.n_cached + n]
             batch = Batch(t(ids), t(pos), t(slots), t(bt), t(lens), t(qlens), len(seqs), S, True, 1, t(last).long())
+            self._attach_kv_rounds(batch, bt, lens, qlens, None, S)
         if any(s.cross_blocks for s in seqs):
             fresh = [s for s in seqs if s.cross_blocks and not s._img_encoded]
             if fresh:
@@ -830,8 +896,10 @@ def bench_decode_throughput(args, rank, world):
            "deepseek_r1_distill_70b": LlamaConfig.deepseek_r1_distill_70b}[name]()
     B, P, G = args.batch, args.prompt_len, args.gen_len
     quant = getattr(args, "quantization", None)
+    kvd = getattr(args, "kv_cache_dtype", None)
     eng = LLMEngine(cfg, device=f"cuda:{torch.cuda.current_device()}", max_num_seqs=max(B, 1),
-                    max_model_len=P + G + 64, enable_prefix_caching=False, quantization=quant)
+                    max_model_len=P + G + 64, enable_prefix_caching=False, quantization=quant,
+                    kv_cache_dtype=kvd)
     params = SamplingParams(temperature=0.7, top_k=50, top_p=0.9, max_tokens=G, ignore_eos=True)
     rng = np.random.default_rng(0)
     prompts = lambda: [rng.integers(10, cfg.vocab_size - 10, P).tolist() for _ in range(B)]

@@ -158,6 +158,10 @@ class Batch:
     # packed varlen prefill: T = sum(q_lens) rows, sequence b's rows start at q_start[b] (no padding rows);
     # S is then max(q_lens).  None = the padded [B, S] layout.
     q_start: Optional[torch.Tensor] = None
+    # fp8 KV cache, prefill steps: the bf16 scratch pair ([capacity, Hkv, 64, hd], one layer at a time, reused by
+    # every layer) and the host-built dequant + attention rounds (ops.build_kv_rounds); None with a bf16 cache
+    kv_scratch: Optional[tuple] = None
+    kv_rounds: Optional[list] = None
 
 
 class LlamaAttention(nn.Module):
@@ -172,34 +176,42 @@ class LlamaAttention(nn.Module):
         self.hk = self.qkv_proj.kv_local
         self.hd = cfg.head_dim
         self.scale = 1.0 / math.sqrt(cfg.head_dim)
+        # fp8 KV cache: this layer's scalar scales (value = code * scale; vLLM's k_scale / v_scale), identical on
+        # every TP rank; plain floats so that a checkpoint loader can fill them.  Unused with a bf16 cache.
+        self.k_scale = 1.0
+        self.v_scale = 1.0
 
     def forward(self, x, batch: Batch, k_cache, v_cache, cos, sin, residual=None, rms_eps=None):
         T = x.shape[0]
         h, hk, hd = self.h, self.hk, self.hd
+        ks, vs = self.k_scale, self.v_scale
         qp = self.qkv_proj
         if (not batch.is_prefill and FUSED_DECODE and QKV_FOLD_IN_ATTN and rms_eps is not None and x.is_cuda
                 and (batch.num_splits or 1) <= QKV_FOLD_MAX_SPLITS and T <= 64 and qp.bias is None and qp.w_scale is None and qp.weight.dtype == torch.bfloat16
                 and x.is_contiguous() and x.shape[1] >= 2048):
             o = ops.decode_attention_rope_qkv(x, qp.weight, rms_eps, k_cache, v_cache, batch.block_table,
                                               batch.ctx_lens, batch.positions, cos, sin, batch.slots, h, hk,
-                                              self.scale, num_splits=batch.num_splits)
+                                              self.scale, num_splits=batch.num_splits, k_scale=ks, v_scale=vs)
             return self.o_proj(o, residual=residual)
         qkv = qp(x, rms_eps=rms_eps)  # [T, (h + 2hk) * hd]
         if not batch.is_prefill and FUSED_DECODE:  # RoPE + KV-cache write inside the decode attention kernel
             o = ops.decode_attention_rope(qkv, k_cache, v_cache, batch.block_table, batch.ctx_lens, batch.positions,
-                                          cos, sin, batch.slots, h, hk, self.scale, num_splits=batch.num_splits)
+                                          cos, sin, batch.slots, h, hk, self.scale, num_splits=batch.num_splits,
+                                          k_scale=ks, v_scale=vs)
             return self.o_proj(o, residual=residual)
-        ops.rope_qkv_cache(qkv, batch.positions, cos, sin, k_cache, v_cache, batch.slots, h, hk)
+        ops.rope_qkv_cache(qkv, batch.positions, cos, sin, k_cache, v_cache, batch.slots, h, hk, ks, vs)
         q = qkv[:, : h * hd].view(T, h, hd)
         if batch.is_prefill and batch.q_start is not None:
             o = ops.paged_attention_varlen(q, k_cache, v_cache, batch.block_table, batch.ctx_lens, batch.q_lens,
-                                           batch.q_start, batch.S, self.scale).view(T, h * hd)
+                                           batch.q_start, batch.S, self.scale, k_scale=ks, v_scale=vs,
+                                           scratch=batch.kv_scratch, rounds=batch.kv_rounds).view(T, h * hd)
         elif batch.is_prefill:
             o = ops.paged_attention(q.view(batch.B, batch.S, h, hd), k_cache, v_cache, batch.block_table,
-                                    batch.ctx_lens, batch.q_lens, self.scale, causal=True).view(T, h * hd)
+                                    batch.ctx_lens, batch.q_lens, self.scale, causal=True, k_scale=ks, v_scale=vs,
+                                    scratch=batch.kv_scratch, rounds=batch.kv_rounds).view(T, h * hd)
         else:
             o = ops.decode_attention(q, k_cache, v_cache, batch.block_table, batch.ctx_lens, self.scale,
-                                     num_splits=batch.num_splits).view(T, h * hd)
+                                     num_splits=batch.num_splits, k_scale=ks, v_scale=vs).view(T, h * hd)
         return self.o_proj(o, residual=residual)
 
 
@@ -313,5 +325,7 @@ def allocate_kv_cache(cfg: LlamaConfig, kv_heads_local: int, num_blocks: int, de
     return buf, [(buf[i, 0], buf[i, 1]) for i in range(cfg.num_hidden_layers)]
 
 
-def kv_bytes_per_block(cfg: LlamaConfig, kv_heads_local: int) -> int:
-    return cfg.num_hidden_layers * 2 * kv_heads_local * KV_BLOCK * cfg.head_dim * 2
+def kv_bytes_per_block(cfg: LlamaConfig, kv_heads_local: int, dtype=torch.bfloat16) -> int:
+    """Bytes of one 64-token block across all layers (K and V) at the cache dtype (bf16: 2 bytes, fp8: 1)."""
+    esize = torch.empty((), dtype=dtype).element_size()
+    return cfg.num_hidden_layers * 2 * kv_heads_local * KV_BLOCK * cfg.head_dim * esize

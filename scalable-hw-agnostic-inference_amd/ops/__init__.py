@@ -12,7 +12,8 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional, Tuple
+from dataclasses import dataclass
+from typing import List, Optional, Sequence, Tuple
 
 import torch
 
@@ -26,6 +27,8 @@ __all__ = [
     "paged_attention", "decode_attention", "kv_write", "rope", "rope_pairs", "gated_act", "bias_act", "sched_step",
     "softmax_", "embedding", "token_feedback", "decode_attention_rope", "decode_attention_rope_qkv", "gemm_partials", "quantize_fp8_rows", "dequant_fp8", "quantize_mxfp4", "dequant_mxfp4", "mxfp4_pack", "mxfp4_unpack", "is_mxfp4", "quant_rows_fp8", "gemm_f8", "pack_conv_weight", "pack_up2_phase_weight", "linear_wslices", "unpack_conv_weight", "act_id", "ACT_NONE", "ACT_SILU", "ACT_GELU",
     "ACT_GELU_TANH", "ACT_QUICK_GELU", "ACT_RELU", "decode_splits", "set_decode_wb",
+    "paged_attention_varlen", "rope_qkv_cache", "quantize_kv_fp8", "dequant_kv_fp8", "kv_dequant_blocks",
+    "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE",
 ]
 
 
@@ -580,12 +583,149 @@ def attention(q, k, v, scale: Optional[float] = None, causal: bool = False, caus
     return o
 
 
-def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=None, causal=True):
-    """Prefill attention over a paged KV cache (64-token blocks)."""
+# ----------------------------------------------------------------------------- fp8 (OCP e4m3fn) KV cache
+FP8_KV_DTYPE = ref.FP8_KV_DTYPE
+
+
+def _kv8(k_cache, v_cache) -> bool:
+    """True for an fp8 cache pair; a mixed pair is an error on every path."""
+    ref._check_kv_pair(k_cache, v_cache)
+    return k_cache.dtype == FP8_KV_DTYPE
+
+
+def quantize_kv_fp8(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
+    """The fp8 KV-cache quantisation rule: RNE e4m3fn of clamp(float(x) * (1 / scale), -448, 448)."""
+    return ref.quantize_kv_fp8(x, scale)
+
+
+def dequant_kv_fp8(c: torch.Tensor, scale: float = 1.0, dtype=torch.bfloat16) -> torch.Tensor:
+    """float(code) * scale, rounded once to ``dtype``."""
+    return ref.dequant_kv_fp8(c, scale, dtype)
+
+
+def kv_dequant_blocks(k_cache, v_cache, phys, k_out, v_out, k_scale: float = 1.0, v_scale: float = 1.0):
+    """Widen the fp8 cache blocks ``phys`` [n] into blocks 0 .. n-1 of the bf16 scratch caches ``k_out`` / ``v_out``
+    [capacity, Hkv, 64, D] (value = float(code) * scale).  One launch for K and V."""
+    if not _gpu(k_cache):
+        return ref.kv_dequant_blocks(k_cache, v_cache, phys, k_out, v_out, k_scale, v_scale)
+    if not _kv8(k_cache, v_cache):
+        raise ValueError(f"kv_dequant_blocks needs float8_e4m3fn caches, got {k_cache.dtype}")
+    _K().kv_dequant_blocks(k_cache, v_cache, _i32(phys), k_out, v_out, float(k_scale), float(v_scale))
+
+
+@dataclass
+class KVRound:
+    """One dequant + attention round of a prefill step over an fp8 cache: the cache blocks ``phys`` are widened into
+    scratch blocks 0 .. n-1 and the sequences ``sel`` of the step attend them through ``block_table`` (remapped to
+    scratch indices).  Rounds cover every sequence of the step exactly once; sequences write disjoint q rows."""
+    phys: torch.Tensor                 # [n] int32 cache block ids
+    block_table: torch.Tensor          # [b, max_blocks] int32 scratch block ids
+    kv_lens: torch.Tensor              # [b] int32
+    q_lens: Optional[torch.Tensor]     # [b] int32
+    q_start: Optional[torch.Tensor]    # [b] int32 (packed varlen layout) or None (padded [B, S] layout)
+    max_q: int
+    sel: Optional[torch.Tensor]        # [b] int64 sequence rows of this round; None = all of the step's sequences
+    n_blocks: int = 0
+
+
+def plan_kv_scratch(need: Sequence[int], capacity: int) -> List[List[int]]:
+    """Group sequences (in order) so that each group's cache blocks fit a scratch of ``capacity`` blocks: ``need[i]``
+    is sequence i's block count.  Every sequence lands in exactly one group; a single sequence larger than the
+    scratch cannot be attended and raises."""
+    groups: List[List[int]] = []
+    cur: List[int] = []
+    used = 0
+    for i, n in enumerate(need):
+        n = int(n)
+        if n > capacity:
+            raise ValueError(f"sequence {i} needs {n} KV blocks but the dequantisation scratch holds {capacity}")
+        if cur and used + n > capacity:
+            groups.append(cur)
+            cur, used = [], 0
+        cur.append(i)
+        used += n
+    if cur:
+        groups.append(cur)
+    return groups
+
+
+def build_kv_rounds(block_table, kv_lens, q_lens, q_start, capacity: int, device, max_q: Optional[int] = None
+                    ) -> List[KVRound]:
+    """Host-side plan of a prefill step over an fp8 cache (all inputs host arrays: no device sync): the rounds of
+    :func:`plan_kv_scratch` with their remapped block tables, uploaded once."""
+    import numpy as np
+    bt = np.asarray(block_table, dtype=np.int32)
+    kvl = np.asarray(kv_lens, dtype=np.int32)
+    ql = None if q_lens is None else np.asarray(q_lens, dtype=np.int32)
+    qs = None if q_start is None else np.asarray(q_start, dtype=np.int32)
+    B, mb = bt.shape
+    need = (kvl.astype(np.int64) + 63) // 64
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device, non_blocking=True)
+    rounds = []
+    groups = plan_kv_scratch(need, capacity)
+    for g in groups:
+        rbt = np.zeros((len(g), mb), dtype=np.int32)
+        phys, off = [], 0
+        for r, i in enumerate(g):
+            n = int(need[i])
+            phys.append(bt[i, :n])
+            rbt[r, :n] = np.arange(off, off + n, dtype=np.int32)
+            off += n
+        phys = np.concatenate(phys) if phys else np.zeros(0, np.int32)
+        gi = np.asarray(g, dtype=np.int64)
+        mq = int(ql[gi].max()) if (ql is not None and qs is not None) else int(max_q or 0)
+        rounds.append(KVRound(t(phys), t(rbt), t(kvl[gi]), None if ql is None else t(ql[gi]),
+                              None if qs is None else t(qs[gi]), mq, None if len(groups) == 1 else t(gi), off))
+    return rounds
+
+
+def _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q, scale, causal, k_scale, v_scale,
+               scratch, rounds):
+    """Prefill attention over an fp8 cache: widen the blocks a round needs into the bf16 scratch, run the bf16
+    kernel on it with the remapped table.  Without ``rounds`` (operator-level calls) the plan is built here from
+    the device metadata, which synchronises; the engine passes the plan it made while building the batch."""
+    if rounds is None:
+        cap = scratch[0].shape[0] if scratch is not None else None
+        need = int(((kv_lens.cpu().long() + 63) // 64).sum())
+        rounds = build_kv_rounds(block_table.cpu().numpy(), kv_lens.cpu().numpy(),
+                                 None if q_lens is None else q_lens.cpu().numpy(),
+                                 None if q_start is None else q_start.cpu().numpy(), cap if cap is not None else
+                                 max(need, 1), q.device, max_q)
+    if scratch is None:
+        cap = max(max(r.n_blocks for r in rounds), 1)
+        shape = (cap,) + tuple(k_cache.shape[1:])
+        scratch = (torch.empty(shape, dtype=q.dtype, device=q.device), torch.empty(shape, dtype=q.dtype,
+                                                                                   device=q.device))
+    ks, vs = scratch
+    o = torch.zeros(q.shape, dtype=q.dtype, device=q.device) if len(rounds) != 1 else torch.empty(
+        q.shape, dtype=q.dtype, device=q.device)
+    for r in rounds:
+        kv_dequant_blocks(k_cache, v_cache, r.phys, ks, vs, k_scale, v_scale)
+        if q_start is not None:   # packed rows: the round's sequences address their own rows of q / o
+            _K().paged_attn_varlen(q, ks, vs, o, r.block_table, r.kv_lens, r.q_lens, r.q_start, int(r.max_q),
+                                   float(scale), bool(causal))
+        elif r.sel is None:
+            _K().flash_attn(q, ks, vs, o, float(scale), bool(causal), 0, r.kv_lens, r.q_lens, None, r.block_table)
+        else:
+            qs_ = q.index_select(0, r.sel)
+            os_ = torch.empty_like(qs_)
+            _K().flash_attn(qs_, ks, vs, os_, float(scale), bool(causal), 0, r.kv_lens, r.q_lens, None,
+                            r.block_table)
+            o.index_copy_(0, r.sel, os_)
+    return o
+
+
+def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=None, causal=True,
+                    k_scale: float = 1.0, v_scale: float = 1.0, scratch=None, rounds=None):
+    """Prefill attention over a paged KV cache (64-token blocks).  An fp8 cache (``k_scale`` / ``v_scale``) is
+    widened block-wise into the bf16 ``scratch`` pair ([capacity, Hkv, 64, D]) in one or more ``rounds``."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if not _gpu(q):
-        return ref.paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale, causal)
+        return ref.paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale, causal, k_scale, v_scale)
+    if _kv8(k_cache, v_cache):
+        return _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, None, q.shape[1], scale, causal,
+                          k_scale, v_scale, scratch, rounds)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     _K().flash_attn(q, k_cache, v_cache, o, float(scale), bool(causal), 0, _i32(kv_lens), _i32(q_lens), None,
                     _i32(block_table))
@@ -593,13 +733,17 @@ def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=Non
 
 
 def paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q: int, scale=None,
-                           causal=True):
+                           causal=True, k_scale: float = 1.0, v_scale: float = 1.0, scratch=None, rounds=None):
     """Packed (varlen) prefill attention over a paged KV cache: q [T, Hq, D] holds every sequence's new tokens
     back to back (sequence b = rows q_start[b] .. + q_lens[b] - 1), so no padding rows are computed."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if not _gpu(q):
-        return ref.paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, scale, causal)
+        return ref.paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, scale, causal,
+                                          k_scale, v_scale)
+    if _kv8(k_cache, v_cache):
+        return _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q, scale, causal, k_scale,
+                          v_scale, scratch, rounds)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     _K().paged_attn_varlen(q, k_cache, v_cache, o, _i32(block_table), _i32(kv_lens), _i32(q_lens), _i32(q_start),
                            int(max_q), float(scale), bool(causal))
@@ -620,25 +764,33 @@ def decode_splits(batch: int, hkv: int, max_ctx: int) -> int:
     return int(min(nblk, want, 64))
 
 
+def _kv8_kw(k_cache, v_cache, k_scale, v_scale) -> dict:
+    """Extra kernel arguments of an fp8 cache (none for bf16: those calls stay exactly as they were)."""
+    return {"k_scale": float(k_scale), "v_scale": float(v_scale)} if _kv8(k_cache, v_cache) else {}
+
+
 def decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale=None, num_splits: Optional[int] = None,
-                     max_ctx: Optional[int] = None, out=None):
-    """Paged single-token decode attention. q [B,Hq,D]."""
+                     max_ctx: Optional[int] = None, out=None, k_scale: float = 1.0, v_scale: float = 1.0):
+    """Paged single-token decode attention. q [B,Hq,D].  An fp8 cache (dtype float8_e4m3fn, values = code * scale)
+    always runs the split kernel's fp8 form."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if not _gpu(q):
-        return ref.decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale)
+        return ref.decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale, k_scale, v_scale)
     B, Hq, _ = q.shape
     if num_splits is None:
         mc = max_ctx if max_ctx is not None else block_table.shape[1] * 64
         num_splits = decode_splits(B, k_cache.shape[1], mc)
     ws = torch.empty(B * Hq * num_splits * (D + 2), dtype=torch.float32, device=q.device)
     o = out if out is not None else torch.empty(q.shape, dtype=q.dtype, device=q.device)
-    _K().decode_attn(q, k_cache, v_cache, o, _i32(block_table), _i32(ctx_lens), ws, int(num_splits), float(scale))
+    _K().decode_attn(q, k_cache, v_cache, o, _i32(block_table), _i32(ctx_lens), ws, int(num_splits), float(scale),
+                     **_kv8_kw(k_cache, v_cache, k_scale, v_scale))
     return o
 
 
 def decode_attention_rope(qkv, k_cache, v_cache, block_table, ctx_lens, positions, cos, sin, slots, h: int, hk: int,
-                          scale=None, num_splits: Optional[int] = None, max_ctx: Optional[int] = None, out=None):
+                          scale=None, num_splits: Optional[int] = None, max_ctx: Optional[int] = None, out=None,
+                          k_scale: float = 1.0, v_scale: float = 1.0):
     """One fused decode step on the packed QKV rows qkv [B, (h + 2 hk) D]: NeoX RoPE on q / k, this step's k / v
     written into the paged caches at ``slots`` (-1: padding row), attention over the cached context plus the
     new token (``ctx_lens`` count it).  Equivalent to rope_qkv_cache + decode_attention.  Returns [B, h D]."""
@@ -646,16 +798,18 @@ def decode_attention_rope(qkv, k_cache, v_cache, block_table, ctx_lens, position
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     B = qkv.shape[0]
     if not _gpu(qkv):
-        rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, h, hk)
+        rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, h, hk, k_scale, v_scale)
         q = qkv[:, : h * D].reshape(B, h, D)
-        return decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale).reshape(B, h * D)
+        return decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale, k_scale=k_scale,
+                                v_scale=v_scale).reshape(B, h * D)
     if num_splits is None:
         mc = max_ctx if max_ctx is not None else block_table.shape[1] * 64
         num_splits = decode_splits(B, hk, mc)
     ws = torch.empty(B * h * num_splits * (D + 2), dtype=torch.float32, device=qkv.device)
     o = out if out is not None else torch.empty(B, h * D, dtype=qkv.dtype, device=qkv.device)
     _K().decode_attn_rope(qkv, k_cache, v_cache, o, _i32(block_table), _i32(ctx_lens), _i32(positions), cos, sin,
-                          _i32(slots), ws, int(h), int(hk), int(num_splits), float(scale))
+                          _i32(slots), ws, int(h), int(hk), int(num_splits), float(scale),
+                          **_kv8_kw(k_cache, v_cache, k_scale, v_scale))
     return o
 
 
@@ -667,13 +821,15 @@ def gemm_partials(x, w, rms_eps: float) -> torch.Tensor:
 
 
 def decode_attention_rope_qkv(x, w_qkv, rms_eps: float, k_cache, v_cache, block_table, ctx_lens, positions, cos, sin,
-                              slots, h: int, hk: int, scale=None, num_splits: Optional[int] = None, out=None):
+                              slots, h: int, hk: int, scale=None, num_splits: Optional[int] = None, out=None,
+                              k_scale: float = 1.0, v_scale: float = 1.0):
     """decode_attention_rope on qkv = linear(rmsnorm(x), w_qkv) (norm gain folded into w_qkv) with the QKV GEMM's
     split-K fold done inside the attention kernel.  Same values as the two-step form: the kernel adds the partial
     slabs in the fold's order and rounds q / k / v to bf16 as the fold's epilogue does.  Returns [B, h D]."""
     if not _gpu(x):
         return decode_attention_rope(linear(x, w_qkv, rms_eps=rms_eps), k_cache, v_cache, block_table, ctx_lens,
-                                     positions, cos, sin, slots, h, hk, scale, num_splits, out=out)
+                                     positions, cos, sin, slots, h, hk, scale, num_splits, out=out, k_scale=k_scale,
+                                     v_scale=v_scale)
     D = k_cache.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     B, K = x.shape
@@ -687,14 +843,15 @@ def decode_attention_rope_qkv(x, w_qkv, rms_eps: float, k_cache, v_cache, block_
     # qkv slot: the (read-only) partials stand in -- never an alias of the mutated output o
     _K().decode_attn_rope(part, k_cache, v_cache, o, _i32(block_table), _i32(ctx_lens), _i32(positions), cos, sin,
                           _i32(slots), ws, int(h), int(hk), int(num_splits), float(scale), part, int(kg), int(K),
-                          float(rms_eps))
+                          float(rms_eps), **_kv8_kw(k_cache, v_cache, k_scale, v_scale))
     return o
 
 
-def kv_write(k, v, k_cache, v_cache, slots):
+def kv_write(k, v, k_cache, v_cache, slots, k_scale: float = 1.0, v_scale: float = 1.0):
+    """k / v [T, Hkv, D] into the paged caches at ``slots``; an fp8 cache stores quantize_kv_fp8(x, scale)."""
     if not _gpu(k):
-        return ref.kv_write(k, v, k_cache, v_cache, slots)
-    _K().kv_write(k, v, k_cache, v_cache, _i32(slots))
+        return ref.kv_write(k, v, k_cache, v_cache, slots, k_scale, v_scale)
+    _K().kv_write(k, v, k_cache, v_cache, _i32(slots), **_kv8_kw(k_cache, v_cache, k_scale, v_scale))
 
 
 # ----------------------------------------------------------------------------- elementwise
@@ -707,7 +864,8 @@ def rope(x, positions, cos, sin, rot_dim: Optional[int] = None, neox: bool = Tru
     return x
 
 
-def rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, heads: int, kv_heads: int):
+def rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, heads: int, kv_heads: int,
+                   k_scale: float = 1.0, v_scale: float = 1.0):
     """Packed QKV rows [T, (H + 2Hkv) * D]: NeoX RoPE on q in place, rotated k and v written to the paged
     caches [blocks, Hkv, 64, D] at ``slots`` (-1 = skip).  One fused kernel on the GPU."""
     T = qkv.shape[0]
@@ -718,9 +876,10 @@ def rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, heads: int
         v = qkv[:, (heads + kv_heads) * D:].view(T, kv_heads, D)
         ref.rope(q, positions, cos, sin, D, True)
         ref.rope(k, positions, cos, sin, D, True)
-        ref.kv_write(k, v, k_cache, v_cache, slots)
+        ref.kv_write(k, v, k_cache, v_cache, slots, k_scale, v_scale)
         return qkv
-    _K().rope_qkv_cache(qkv, _i32(positions), cos, sin, k_cache, v_cache, _i32(slots), int(heads), int(kv_heads))
+    _K().rope_qkv_cache(qkv, _i32(positions), cos, sin, k_cache, v_cache, _i32(slots), int(heads), int(kv_heads),
+                        **_kv8_kw(k_cache, v_cache, k_scale, v_scale))
     return qkv
 
 

@@ -370,49 +370,94 @@ def attention(q, k, v, scale=None, causal=False, causal_offset=0, kv_lens=None, 
     return o.to(q.dtype)
 
 
-def gather_paged(cache, block_table, length):
-    """cache [blocks, H, 64, D], table row -> [length, H, D]"""
+FP8_KV_DTYPE = torch.float8_e4m3fn   # OCP e4m3fn (not fnuz)
+FP8_KV_MAX = 448.0
+
+
+def quantize_kv_fp8(x, scale=1.0):
+    """The fp8 KV-cache quantisation rule (the oracle every writer is tested against):
+    code = RNE fp8(clamp(float(x) * (1 / scale), -448, 448)), with 1 / scale computed once in fp32 and the clamp
+    applied in fp32 BEFORE the conversion (torch's conversion returns NaN above 464 without it)."""
+    inv = (torch.ones((), dtype=torch.float32) / torch.tensor(float(scale), dtype=torch.float32)).to(x.device)
+    return (x.float() * inv).clamp(-FP8_KV_MAX, FP8_KV_MAX).to(FP8_KV_DTYPE)
+
+
+def dequant_kv_fp8(c, scale=1.0, dtype=torch.float32):
+    """value = float(code) * scale (fp32 product, then one rounding to ``dtype``)."""
+    return (c.float() * torch.tensor(float(scale), dtype=torch.float32, device=c.device)).to(dtype)
+
+
+def is_fp8_kv(cache) -> bool:
+    return cache.dtype == FP8_KV_DTYPE
+
+
+def _check_kv_pair(k_cache, v_cache):
+    if is_fp8_kv(k_cache) != is_fp8_kv(v_cache):
+        raise ValueError(f"k_cache / v_cache dtypes differ ({k_cache.dtype} vs {v_cache.dtype})")
+
+
+def gather_paged(cache, block_table, length, scale=1.0):
+    """cache [blocks, H, 64, D], table row -> [length, H, D]; an fp8 cache is dequantised to fp32"""
     nb = (length + 63) // 64
     blocks = cache[block_table[:nb].long()]  # [nb, H, 64, D]
+    if is_fp8_kv(cache):
+        blocks = dequant_kv_fp8(blocks, scale)
     return blocks.permute(0, 2, 1, 3).reshape(nb * 64, cache.shape[1], cache.shape[3])[:length]
 
 
-def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=None, causal=True):
+def kv_dequant_blocks(k_cache, v_cache, phys, k_out, v_out, k_scale=1.0, v_scale=1.0):
+    """scratch block i = dequantised fp8 cache block phys[i] (k_out / v_out [capacity, H, 64, D])."""
+    n = int(phys.numel())
+    if n > k_out.shape[0]:
+        raise ValueError(f"kv_dequant_blocks: {n} blocks do not fit the scratch capacity {k_out.shape[0]}")
+    k_out[:n] = dequant_kv_fp8(k_cache[phys.long()], k_scale, k_out.dtype)
+    v_out[:n] = dequant_kv_fp8(v_cache[phys.long()], v_scale, v_out.dtype)
+
+
+def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=None, causal=True, k_scale=1.0,
+                    v_scale=1.0):
+    _check_kv_pair(k_cache, v_cache)
     B, Sq, Hq, D = q.shape
     out = torch.zeros_like(q)
     for b in range(B):
         L = int(kv_lens[b])
         ql = int(q_lens[b]) if q_lens is not None else Sq
-        k = gather_paged(k_cache, block_table[b], L)[None]
-        v = gather_paged(v_cache, block_table[b], L)[None]
+        k = gather_paged(k_cache, block_table[b], L, k_scale)[None]
+        v = gather_paged(v_cache, block_table[b], L, v_scale)[None]
         o = attention(q[b:b + 1, :ql], k, v, scale=scale, causal=causal, causal_offset=L - ql)
         out[b, :ql] = o[0]
     return out
 
 
-def paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, scale=None, causal=True):
+def paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, scale=None, causal=True,
+                           k_scale=1.0, v_scale=1.0):
     """q [T, Hq, D] packed (sequence b = rows q_start[b] .. + q_lens[b] - 1)."""
+    _check_kv_pair(k_cache, v_cache)
     out = torch.zeros_like(q)
     for b in range(block_table.shape[0]):
         L, ql, q0 = int(kv_lens[b]), int(q_lens[b]), int(q_start[b])
-        k = gather_paged(k_cache, block_table[b], L)[None]
-        v = gather_paged(v_cache, block_table[b], L)[None]
+        k = gather_paged(k_cache, block_table[b], L, k_scale)[None]
+        v = gather_paged(v_cache, block_table[b], L, v_scale)[None]
         out[q0:q0 + ql] = attention(q[None, q0:q0 + ql], k, v, scale=scale, causal=causal, causal_offset=L - ql)[0]
     return out
 
 
-def decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale=None):
+def decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale=None, k_scale=1.0, v_scale=1.0):
+    _check_kv_pair(k_cache, v_cache)
     B, Hq, D = q.shape
     out = torch.empty_like(q)
     for b in range(B):
         L = int(ctx_lens[b])
-        k = gather_paged(k_cache, block_table[b], L)[None]
-        v = gather_paged(v_cache, block_table[b], L)[None]
+        k = gather_paged(k_cache, block_table[b], L, k_scale)[None]
+        v = gather_paged(v_cache, block_table[b], L, v_scale)[None]
         out[b] = attention(q[b:b + 1, None], k, v, scale=scale)[0, 0]
     return out
 
 
-def kv_write(k, v, k_cache, v_cache, slots):
+def kv_write(k, v, k_cache, v_cache, slots, k_scale=1.0, v_scale=1.0):
+    _check_kv_pair(k_cache, v_cache)
+    if is_fp8_kv(k_cache):  # an fp8 cache stores the codes of quantize_kv_fp8
+        k, v = quantize_kv_fp8(k, k_scale), quantize_kv_fp8(v, v_scale)
     for t in range(k.shape[0]):
         s = int(slots[t])
         if s < 0:

@@ -15,7 +15,11 @@ variant's behaviour).  Engine kwargs come from a /vllm_config.yaml-style file
 (rounded to 64-token KV blocks), quantization (``fp8``: e4m3 weights + per-row
 scales, bf16 activations; ``mxfp4``: OCP MXFP4 weights -- e2m1 codes with one
 e8m0 scale per 32 inputs, quantised on load -- bf16 activations: the 4-bit
-deployment of the reference's bitsandbytes ``load_in_4bit`` models).
+deployment of the reference's bitsandbytes ``load_in_4bit`` models) and
+kv_cache_dtype (``auto`` / ``bf16``, or ``fp8`` / ``fp8_e4m3``: OCP e4m3fn KV
+cache with scalar k/v scales -- half the KV bytes per decode step, twice the
+tokens per block pool; every TP rank reads the same file, so the relaunched
+ranks build the same cache).
 
 Tensor parallelism (``tensor_parallel_size: N``, app/vllm_model_api.py:127-129 with
 cova/mllama-32-11b-vllm-trn1-config.yaml:9): the worker runs as N processes, one
@@ -66,7 +70,8 @@ def build_engine(env: ServerEnv, vc: Optional[dict] = None):
     eng = LLMEngine(cfg, device=env.torch_device, model_path=env.model_path,
                     max_num_seqs=int(vc.get("max_num_seqs", 64)),
                     max_model_len=int(vc.get("max_model_len", min(8192, text.max_position_embeddings))),
-                    enable_prefix_caching=True, quantization=vc.get("quantization"))
+                    enable_prefix_caching=True, quantization=vc.get("quantization"),
+                    kv_cache_dtype=vc.get("kv_cache_dtype"))
     import torch
     with torch.inference_mode():
         # every decode batch bucket (sampled and all-greedy) captured before the first request

@@ -3,6 +3,7 @@
 (hipBLASLt GEMM, MIOpen conv, SDPA) on the same random bf16 inputs.
 
 python tools/bench_kernels.py [--only gemm,conv,attn,norm] [--json out.json]
+(--only kv8: decode attention over bf16 vs fp8 KV caches)
 """
 import argparse
 import json
@@ -373,6 +374,82 @@ def bench_dattn_long(rows):
             rows.append(r)
 
 
+def bench_kv8(rows):
+    """Fused decode attention (Mistral-7B layer: 32 q / 8 KV heads, D 128) over a bf16 and an fp8 (e4m3fn) paged
+    cache, each with the routing and split count the engine would use, graph-replayed (host out of the loop) in
+    three alternating repetitions; min / max over the repetitions show the spread.  Calls rotate over enough
+    cache copies (>= 1 GB of bf16 K + V) that no launch finds its blocks in the Infinity Cache."""
+    h, hk, D = 32, 8, 128
+    shapes = [(64, 192), (64, 1024), (256, 1024), (1, 65536)]
+    if os.environ.get("SHAI_KV8_SHAPES"):  # e.g. "64x192,1x65536": batch x context
+        shapes = [tuple(int(v) for v in t.split("x")) for t in os.environ["SHAI_KV8_SHAPES"].split(",")]
+
+    def replayer(fn, iters):
+        fn()
+        torch.cuda.synchronize()
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            fn()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=s):
+                for _ in range(iters):
+                    fn()
+        torch.cuda.synchronize()
+
+        def run():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            g.replay()
+            e1.record()
+            torch.cuda.synchronize()
+            return e0.elapsed_time(e1) / iters * 1e3   # us per call
+        return run
+
+    for B, ctx in shapes:
+        nblk = (ctx + 63) // 64
+        per_copy = B * nblk * hk * 64 * D * 2 * 2
+        ncopy = min(16, max(1, -(-(1 << 30) // per_copy)))
+        pool = ncopy * B * nblk + 8
+        bts = torch.randperm(pool, device="cuda")[:ncopy * B * nblk].view(ncopy, B, nblk).int()
+        k16, v16 = rnd(pool, hk, 64, D), rnd(pool, hk, 64, D)
+        caches = {"bf16": (k16, v16), "fp8": (ops.quantize_kv_fp8(k16, 1.0), ops.quantize_kv_fp8(v16, 1.0))}
+        ctx_l = torch.full((B,), ctx, device="cuda", dtype=torch.int32)
+        pos = ctx_l - 1
+        cos, sin = torch.rand(ctx + 1, D // 2, device="cuda"), torch.rand(ctx + 1, D // 2, device="cuda")
+        slots = (bts[:, :, (ctx - 1) // 64] * 64 + (ctx - 1) % 64).int().contiguous()
+        qkv = rnd(B, (h + 2 * hk) * D)
+        splits, need = ops.decode_splits(B, hk, ctx), 1   # the engine's rule (LLMEngine.decode_splits)
+        while need < 64 and need * 1024 < ctx:
+            need *= 2
+        splits = max(splits, min(need, nblk))
+        iters = max(16, 2 * ncopy)
+        runs = {}
+        for name, (kc, vc) in caches.items():
+            o = torch.empty(B, h * D, device="cuda", dtype=torch.bfloat16)
+            state = {"i": 0}
+
+            def fn(kc=kc, vc=vc, o=o, state=state):
+                i = state["i"] % ncopy
+                state["i"] += 1
+                ops.decode_attention_rope(qkv, kc, vc, bts[i], ctx_l, pos, cos, sin, slots[i], h, hk,
+                                          num_splits=splits, out=o)
+            runs[name] = replayer(fn, iters)
+        t = {name: [] for name in runs}
+        for _ in range(3):
+            for name, run in runs.items():
+                t[name].append(min(run() for _ in range(3)))
+        r = dict(op="decode_attn_kv8", shape=f"B{B} ctx{ctx}", splits=splits, copies=ncopy)
+        for name in runs:
+            r[f"{name}_us"] = min(t[name])
+            r[f"{name}_us_max"] = max(t[name])
+            byt = B * hk * (ctx - 1) * D * 2 * (2 if name == "bf16" else 1)
+            r[f"{name}_GBps"] = byt / 1e9 / (min(t[name]) / 1e6)
+        r["fp8_speedup"] = r["bf16_us"] / r["fp8_us"]
+        rows.append(r)
+        del caches, k16, v16
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="gemm,conv,attn,norm")
@@ -383,7 +460,7 @@ def main():
         for name in a.only.split(","):
             {"gemm": bench_gemm, "conv": bench_conv, "attn": bench_attn, "norm": bench_norm,
              "decode": bench_decode, "decode_fp8": bench_decode_fp8, "fp4": bench_fp4, "sdgemm": bench_sdgemm, "f8": bench_f8,
-             "dattn": bench_dattn, "dattn_long": bench_dattn_long}[name](rows)
+             "dattn": bench_dattn, "dattn_long": bench_dattn_long, "kv8": bench_kv8}[name](rows)
     for r in rows:
         print("  ".join(f"{k}={v:.1f}" if isinstance(v, float) else f"{k}={v}" for k, v in r.items()), flush=True)
     if a.json:

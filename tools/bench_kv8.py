@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""LLM decode with a bf16 and an fp8 (OCP e4m3fn) KV cache, crossed with bf16 and MXFP4 weights, one variant after
+another in fresh child processes (each run owns the GPU and its own autotuner cache): ``bench_decode_throughput`` of
+engines/llm.py per variant, one JSON line each, with the engine's block-pool size (num_kv_blocks, and
+kv_blocks_budget: what the memory budget allows before the cap by what max_num_seqs can use) and KV bytes added.  A variant
+is named ``<kv>+<weights>``: bf16+bf16, fp8+bf16, bf16+mxfp4, fp8+mxfp4.
+
+python tools/bench_kv8.py [--llm-model mistral_7b] [--batch 256] [--prompt-len 1024] [--gen-len 64]
+                          [--steps 1] [--warmup 1] [--variants bf16+bf16,fp8+bf16,bf16+mxfp4,fp8+mxfp4]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+VARIANTS = ("bf16+bf16", "fp8+bf16", "bf16+mxfp4", "fp8+mxfp4")
+
+
+def child(a):
+    sys.path.insert(0, ROOT)
+    import torch
+    from shai_amd.engines import llm
+    seen = {}
+    init = llm.LLMEngine.__init__
+
+    def recording_init(self, *args, **kw):
+        init(self, *args, **kw)
+        seen.update(num_kv_blocks=int(self.num_kv_blocks), kv_blocks_budget=self.kv_blocks_budget,
+                    kv_bytes=int(self.kv_bytes),
+                    kv_scratch_bytes=int(self.kv_scratch_bytes), kv_dtype=str(self.kv_buf.dtype))
+    llm.LLMEngine.__init__ = recording_init
+    kv, w = a.child.split("+")
+    ns = argparse.Namespace(batch=a.batch, prompt_len=a.prompt_len, gen_len=a.gen_len, steps=a.steps,
+                            warmup=a.warmup, tp=1, llm_model=a.llm_model, quantization=None if w == "bf16" else w,
+                            kv_cache_dtype=kv)
+    with torch.inference_mode():
+        r = llm.bench_decode_throughput(ns, 0, 1)
+    r["variant"] = a.child
+    r.update(seen)
+    r["kv_gb"] = round(seen.get("kv_bytes", 0) / 1e9, 2)
+    print("BENCH_KV8 " + json.dumps(r), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--llm-model", default="mistral_7b",
+                    choices=["mistral_7b", "llama3_8b", "deepseek_r1_distill_70b"])
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--prompt-len", type=int, default=1024)
+    ap.add_argument("--gen-len", type=int, default=64)
+    ap.add_argument("--steps", type=int, default=1)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--variants", default=",".join(VARIANTS))
+    ap.add_argument("--timeout", type=int, default=900, help="seconds per variant")
+    ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    a = ap.parse_args()
+    if a.child:
+        child(a)
+        return 0
+    for v in a.variants.split(","):
+        assert v in VARIANTS, v
+        cmd = [sys.executable, os.path.abspath(__file__), "--child", v, "--llm-model", a.llm_model,
+               "--batch", str(a.batch), "--prompt-len", str(a.prompt_len), "--gen-len", str(a.gen_len),
+               "--steps", str(a.steps), "--warmup", str(a.warmup)]
+        try:
+            p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=a.timeout)
+        except subprocess.TimeoutExpired:
+            print(json.dumps({"variant": v, "error": f"timed out after {a.timeout} s"}), flush=True)
+            return 1   # nothing more is started on a GPU that may be hung
+        lines = [ln for ln in p.stdout.splitlines() if ln.startswith("BENCH_KV8 ")]
+        if p.returncode != 0 or not lines:
+            print(json.dumps({"variant": v, "error": f"exit {p.returncode}", "tail": p.stdout[-2000:]}), flush=True)
+            return 1   # a failed variant ends the run: nothing more is started on the GPU
+        print(lines[-1][len("BENCH_KV8 "):], flush=True)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
