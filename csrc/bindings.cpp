@@ -1332,48 +1332,57 @@ void paged_attn_varlen(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
   shai::launch_flash_attn(a, stream());
 }
 
-void decode_attn(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& o,
-                 const Tensor& block_table, const Tensor& ctx_lens, const Tensor& ws, int64_t num_splits,
-                 double scale, double k_scale, double v_scale) {
-  check_rows(q, "q");
-  check_rows(o, "o");
-  const bool f8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
-  if (!f8) {
+// What decode_attn and decode_attn_rope share.  The caller has set B, Hq, Hkv, D and its q / o (/ new-token) fields;
+// here: the cache, table and workspace checks, the head-dim / GQA rules of the kernels, the cache, table, split and
+// scale fields, and the launch.
+void decode_attn_launch(shai::DecodeAttnArgs& a, const Tensor& k_cache, const Tensor& v_cache,
+                        const Tensor& block_table, const Tensor& ctx_lens, const Tensor& ws, int64_t num_splits,
+                        double scale, double k_scale, double v_scale) {
+  a.kv_fp8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
+  if (!a.kv_fp8) {
     check_bf16(k_cache, "k_cache");
     check_bf16(v_cache, "v_cache");
   }
   check_i32(block_table, "block_table");
   check_i32(ctx_lens, "ctx_lens");
   check_f32(ws, "ws");
-  SHAI_CHECK(q.dim() == 3 && k_cache.dim() == 4 && k_cache.size(2) == 64, "decode_attn shapes");
-  shai::DecodeAttnArgs a{};
-  a.B = q.size(0);
-  a.Hq = q.size(1);
-  a.D = q.size(2);
-  a.Hkv = k_cache.size(1);
   SHAI_CHECK(a.D == 64 || a.D == 128, "decode_attn head dim 64/128");
   SHAI_CHECK(a.Hq % a.Hkv == 0 && a.Hq / a.Hkv <= 8, "decode_attn GQA group must be <= 8");
-  SHAI_CHECK(q.stride(1) == a.D && o.stride(1) == a.D, "packed heads");
-  a.q = cptr(q);
-  a.o = mptr(o);
-  a.k_cache = cptr(k_cache);
-  a.v_cache = cptr(v_cache);
+  // one wave per query head of the group, and the waves share a block's DMA instructions evenly
+  const int G = a.Hq / a.Hkv;
+  SHAI_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "decode_attn supports GQA groups Hq / Hkv of 1, 2, 4 and 8, got ",
+             G);
+  SHAI_CHECK(k_cache.size(3) == a.D, "decode_attn: cache head dim != q head dim");
+  a.k_cache = k_cache.data_ptr();
+  a.v_cache = v_cache.data_ptr();
   a.block_table = block_table.data_ptr<int>();
   a.ctx_lens = ctx_lens.data_ptr<int>();
   a.max_blocks = block_table.size(1);
   a.num_splits = num_splits;
   a.ws = ws.data_ptr<float>();
   SHAI_CHECK(ws.numel() * 4 >= (long)shai::decode_attn_workspace(a.B, a.Hq, a.D, num_splits), "ws too small");
+  a.scale = scale;
+  if (a.kv_fp8) kv8_scales(a, k_scale, v_scale);
+  shai::launch_decode_attn(a, stream());
+}
+
+void decode_attn(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& o,
+                 const Tensor& block_table, const Tensor& ctx_lens, const Tensor& ws, int64_t num_splits,
+                 double scale, double k_scale, double v_scale) {
+  check_rows(q, "q");
+  check_rows(o, "o");
+  SHAI_CHECK(q.dim() == 3 && k_cache.dim() == 4 && k_cache.size(2) == 64, "decode_attn shapes");
+  shai::DecodeAttnArgs a{};
+  a.B = q.size(0);
+  a.Hq = q.size(1);
+  a.D = q.size(2);
+  a.Hkv = k_cache.size(1);
+  SHAI_CHECK(q.stride(1) == a.D && o.stride(1) == a.D, "packed heads");
+  a.q = cptr(q);
+  a.o = mptr(o);
   a.q_bs = q.stride(0);
   a.o_bs = o.stride(0);
-  a.scale = scale;
-  if (f8) {
-    SHAI_CHECK(k_cache.size(3) == a.D, "decode_attn: cache head dim != q head dim");
-    kv8_scales(a, k_scale, v_scale);
-    shai::launch_decode_attn_kv8(a, stream());
-    return;
-  }
-  shai::launch_decode_attn(a, stream());
+  decode_attn_launch(a, k_cache, v_cache, block_table, ctx_lens, ws, num_splits, scale, k_scale, v_scale);
 }
 
 // Fused decode step on the packed QKV rows [B, (h + 2 hk) D]: RoPE on q and k, this step's k / v into the paged
@@ -1425,16 +1434,8 @@ void decode_attn_rope(const Tensor& qkv, const Tensor& k_cache, const Tensor& v_
   const bool part = qkv_ws.has_value();
   if (!part) check_bf16(qkv, "qkv");  // partials path: qkv is a placeholder (the partials), never read
   check_rows(o, "o");
-  const bool f8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
-  if (!f8) {
-    check_bf16(k_cache, "k_cache");
-    check_bf16(v_cache, "v_cache");
-  }
-  check_i32(block_table, "block_table");
-  check_i32(ctx_lens, "ctx_lens");
   check_i32(positions, "positions");
   check_i32(slots, "slots");
-  check_f32(ws, "ws");
   SHAI_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
                  sin.is_contiguous(), "rope tables: contiguous fp32");
   SHAI_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 64 && k_cache.size(1) == hk, "decode_attn_rope cache shape");
@@ -1443,8 +1444,6 @@ void decode_attn_rope(const Tensor& qkv, const Tensor& k_cache, const Tensor& v_
   a.B = part ? o.size(0) : qkv.size(0);
   a.Hq = h;
   a.Hkv = hk;
-  SHAI_CHECK(a.D == 64 || a.D == 128, "decode_attn head dim 64/128");
-  SHAI_CHECK(a.Hq % a.Hkv == 0 && a.Hq / a.Hkv <= 8, "decode_attn GQA group must be <= 8");
   if (part) {  // q / k / v come from the QKV GEMM's split-K partials (gemm_partials); qkv is not read
     check_f32(*qkv_ws, "qkv_ws");
     const long n = (h + 2 * hk) * a.D;
@@ -1476,25 +1475,11 @@ void decode_attn_rope(const Tensor& qkv, const Tensor& k_cache, const Tensor& v_
   }
   a.o = mptr(o);
   a.o_bs = o.stride(0);
-  a.k_cache = cptr(k_cache);
-  a.v_cache = cptr(v_cache);
-  a.block_table = block_table.data_ptr<int>();
-  a.ctx_lens = ctx_lens.data_ptr<int>();
   a.positions = positions.data_ptr<int>();
   a.slots = slots.data_ptr<int>();
   a.rope_cos = cos.data_ptr<float>();
   a.rope_sin = sin.data_ptr<float>();
-  a.max_blocks = block_table.size(1);
-  a.num_splits = num_splits;
-  a.ws = ws.data_ptr<float>();
-  SHAI_CHECK(ws.numel() * 4 >= (long)shai::decode_attn_workspace(a.B, a.Hq, a.D, num_splits), "ws too small");
-  a.scale = scale;
-  if (f8) {
-    kv8_scales(a, k_scale, v_scale);
-    shai::launch_decode_attn_kv8(a, stream());
-    return;
-  }
-  shai::launch_decode_attn(a, stream());
+  decode_attn_launch(a, k_cache, v_cache, block_table, ctx_lens, ws, num_splits, scale, k_scale, v_scale);
 }
 
 void kv_write(const Tensor& k, const Tensor& v, const Tensor& k_cache, const Tensor& v_cache, const Tensor& slots,

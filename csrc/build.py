@@ -40,9 +40,11 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 KERNEL_SRCS = ["kernels/norm.hip", "kernels/gemm.hip", "kernels/gemm_lds.hip", "kernels/gemm_8ph.hip", "kernels/gemm_w4.hip", "kernels/gemm_ws.hip", "kernels/conv_halo.hip", "kernels/attention.hip", "kernels/attention2.hip", "kernels/attention3.hip", "kernels/elementwise.hip", "kernels/dit.hip",
                "kernels/sampling.hip", "kernels/gemv.hip", "kernels/gemv2.hip", "kernels/gemv_fp4.hip",
                "kernels/gemm_f8.hip", "kernels/attention_kv8.hip"]
-# sources whose kernels must not spill: compiled with the resource-usage remarks on, and build() fails when any of
-# their kernels reports scratch (the hand-scheduled fp8-cache decode kernel sits near its register budget)
-NO_SCRATCH_SRCS = ["kernels/attention_kv8.hip"]
+# kernels that must not spill, as source -> part of the kernel's mangled name: the source is compiled with the
+# resource-usage remarks on, and build() fails when one of the named kernels reports scratch (the fp8-cache
+# instantiations of the hand-scheduled split decode kernel sit near their register budget).  The kernels are picked
+# by name, not by the file a remark prints: that is the file the __global__ template is written in, a header.
+NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8"}
 # per-source extra hipcc flags: gemm_w4's epilogue (256 accumulators x an activation) is larger than LLVM's
 # default pragma-unroll budget; partially unrolled it would index the accumulators at run time (scratch)
 EXTRA_KFLAGS = {"kernels/attention3.hip": "-mllvm -amdgpu-mfma-vgpr-form -fno-slp-vectorize",
@@ -119,7 +121,7 @@ def write_ninja(path: str, out: str = OUT, build_dir: str = BUILD, debug: bool =
             lines.append(f"build {o}: {rule} {os.path.join(CSRC, s)} | {os.path.join(CSRC, 'kernels', 'common.h')} "
                          f"{os.path.join(CSRC, 'kernels', 'launchers.h')}")
             extra = EXTRA_KFLAGS.get(s, "")
-            if s in NO_SCRATCH_SRCS:
+            if s in NO_SCRATCH:
                 extra = (extra + " -Rpass-analysis=kernel-resource-usage").strip()
             if extra:
                 lines.append(f"  kflags = $kflags {extra}")
@@ -146,21 +148,28 @@ def write_ninja(path: str, out: str = OUT, build_dir: str = BUILD, debug: bool =
 LAST_BUILD: dict = {}
 
 
-def check_no_scratch(log: str) -> None:
-    """Fail the build when a kernel of NO_SCRATCH_SRCS spills: its compile prints one 'Function Name' and one
-    'ScratchSize [bytes/lane]' remark per kernel (only when the object was recompiled; a reused object passed
-    this check when it was built)."""
-    names = tuple(os.path.basename(s) for s in NO_SCRATCH_SRCS)
-    fn, bad = "?", []
+def check_no_scratch(log: str) -> list:
+    """Fail the build when a kernel named by NO_SCRATCH spills: a source compiled with the remarks on prints one
+    'Function Name' and one 'ScratchSize [bytes/lane]' remark per kernel (only when the object was recompiled; a
+    reused object passed this check when it was built).  A log that has remarks but none of a named kernel fails
+    too: the kernels were renamed or moved, and the check would pass without looking.  Returns the names checked."""
+    fn, seen, checked, bad = None, False, [], []
     for ln in log.splitlines():
-        if not any(n in ln for n in names):
-            continue
         if "Function Name:" in ln:
             fn = ln.split("Function Name:", 1)[1].split()[0]
-        elif "ScratchSize [bytes/lane]:" in ln and int(ln.split("ScratchSize [bytes/lane]:", 1)[1].split()[0]) > 0:
-            bad.append(f"{fn}: {ln.split('ScratchSize [bytes/lane]:', 1)[1].split()[0]} bytes/lane")
+            seen = True
+            if not any(pat in fn for pat in NO_SCRATCH.values()):
+                fn = None
+        elif fn and "ScratchSize [bytes/lane]:" in ln:
+            checked.append(fn)
+            if int(ln.split("ScratchSize [bytes/lane]:", 1)[1].split()[0]) > 0:
+                bad.append(f"{fn}: {ln.split('ScratchSize [bytes/lane]:', 1)[1].split()[0]} bytes/lane")
     if bad:
         raise RuntimeError("kernels that must not use scratch memory spill: " + "; ".join(bad))
+    if seen and not checked:
+        raise RuntimeError("the no-scratch check found none of its kernels (" + ", ".join(NO_SCRATCH.values()) +
+                           ") in the resource-usage remarks")
+    return checked
 
 
 def build(clean: bool = False, jobs: int | None = None, verbose: bool = False, debug: bool = False) -> dict:
@@ -181,18 +190,18 @@ def build(clean: bool = False, jobs: int | None = None, verbose: bool = False, d
     if verbose:
         cmd.append("-v")
     r = subprocess.run(cmd, cwd=bdir, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    # (the resource-usage remarks of NO_SCRATCH_SRCS are read by check_no_scratch below, not printed)
+    # (the resource-usage remarks of the NO_SCRATCH sources are read by check_no_scratch below, not printed)
     sys.stdout.write("".join(ln for ln in r.stdout.splitlines(True) if "[-Rpass-analysis=" not in ln))
     if r.returncode != 0:
         raise subprocess.CalledProcessError(r.returncode, cmd, r.stdout)
-    if not debug:   # (the debug flavour's device asserts call printf, which takes scratch by itself)
-        check_no_scratch(r.stdout)
+    # (the debug flavour's device asserts call printf, which takes scratch by itself)
+    checked = [] if debug else check_no_scratch(r.stdout)
     # what ninja actually did: "[i/n] HIP <src>" per compiled object, "no work to do" when all were reused
     compiled = [ln.split("] ", 1)[1].split(" ", 1)[1] for ln in r.stdout.splitlines()
                 if ln.startswith("[") and ("] HIP " in ln or "] CXX " in ln)]
     LAST_BUILD.clear()
     LAST_BUILD.update(compiled=compiled, linked=sum("] LINK " in ln for ln in r.stdout.splitlines()),
-                      up_to_date="no work to do" in r.stdout)
+                      up_to_date="no work to do" in r.stdout, no_scratch=checked)
     return targets
 
 
@@ -218,6 +227,8 @@ def main():
     for k, v in t.items():
         print(f"{k}: {v}")
     print(summary())
+    for fn in LAST_BUILD.get("no_scratch", []):
+        print(f"no-scratch check: {fn}")
 
 
 if __name__ == "__main__":

@@ -576,321 +576,10 @@ void launch_flash_attn(const AttnArgs& a, hipStream_t s) {
 }
 
 // ----------------------------------------------------------------------------
-// Paged decode attention (one query token per sequence).
-// grid (B, Hkv, splits); block = G waves (G = Hq/Hkv <= 8), wave w = head hk*G+w.
+// Paged decode attention (one query token per sequence).  The split kernel (decode_attn_kernel: grid over
+// (sequence, KV head, split) items, block = G waves, G = Hq/Hkv in {1, 2, 4, 8}) lives in decode_common.h, one
+// body for the bf16 and the fp8 cache; here are its combine, the wave-per-block kernel and the launcher.
 // ----------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void da_lds_void;
-typedef __bf16 bf16x2d __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8d __attribute__((ext_vector_type(8)));
-#define DA_PAIR(v, i) __builtin_shufflevector(v, v, 2 * (i), 2 * (i) + 1)
-
-// Decode attention, one workgroup per (sequence, KV head, split): G = Hq/Hkv waves, one query head
-// each.  The 64-token K/V blocks stream global -> LDS by LDS-DMA (buffer_load ... lds) into a
-// two-slot ring: block i+1's DMA is in flight while block i is consumed (counted vmcnt of NI
-// instructions per wave per block + one barrier), so HBM latency hides behind the dot products.
-// Per-block buffer descriptors (the cache can exceed 4 GiB) range-check the tail rows past the
-// context: zero-filled, since P = 0 times a never-written NaN pattern would poison P.V.
-// (da_splits, the per-sequence split count, lives in decode_common.h: the fp8-cache kernel shares it)
-
-template <int D, int NI>
-__device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* dsm, const int b, const int hk,
-                                                 const int split) {
-  constexpr int CPR = D / 8;
-  constexpr int RPI = 1024 / (D * 2);           // K/V rows per 1-KB wave DMA instruction
-  constexpr int SLOT = 2 * 64 * D;              // bf16 elements per ring slot (K then V)
-  bf16_t* ring = reinterpret_cast<bf16_t*>(dsm);              // [2][K 64xD swizzled | V 64xD linear]
-  float* sQ = reinterpret_cast<float*>(ring + 2 * SLOT);      // [G][D]
-  float* sP = sQ + 8 * D;                                     // [G][64]
-  const int G = p.Hq / p.Hkv;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int hq = hk * G + w;
-  const bool fused = p.knew != nullptr;
-  const int ctx = p.ctx_lens[b] - (fused ? 1 : 0);  // tokens read from the cache
-  const int nblk = (ctx + 63) / 64;
-  // this sequence's own split count (da_splits): a short sequence in a batch whose split factor was raised for a
-  // long one uses one split -- its other workgroups leave here, before any load
-  const int nsp = da_splits(nblk, p.num_splits);
-  if (split >= nsp) return;
-  const int per = (nblk + nsp - 1) / nsp;
-  const int blk0 = split * per, blk1 = min(nblk, blk0 + per);
-
-  // wave w issues instructions j = w + G*t (t < NI) of the block's 2 * 64 * D * 2 / 1024 = NI * G
-  // physical block ids of this split, 64 per lane-distributed chunk (read ahead, so the ring's
-  // DMA issue never waits on a block-table load queued behind the previous block's DMA)
-  const int* bt = p.block_table + (long)b * p.max_blocks;
-  int chunk0 = blk0;
-  int my_phys = (blk0 + lane < blk1) ? bt[blk0 + lane] : 0;
-  auto phys_of = [&](int bi) {
-    if (bi - chunk0 >= 64) {
-      chunk0 += 64;
-      my_phys = (chunk0 + lane < blk1) ? bt[chunk0 + lane] : 0;
-    }
-    return __builtin_amdgcn_readfirstlane(__shfl(my_phys, bi - chunk0, 64));
-  };
-  auto stage = [&](int slot, int bi) {
-    const int phys = phys_of(bi);
-    const long base = ((long)phys * p.Hkv + hk) * 64 * D;
-    const __amdgpu_buffer_rsrc_t rk = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.k_cache + base),
-                                                                        (short)0, 64 * D * 2, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rv = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.v_cache + base),
-                                                                        (short)0, 64 * D * 2, 0x00020000);
-    bf16_t* dst = ring + slot * SLOT;
-#pragma unroll
-    for (int t = 0; t < NI; ++t) {
-      const int j = w + G * t;                  // 0 .. 64*D*2*2/1024 - 1
-      const bool isv = j >= NI * G / 2;
-      const int jj = isv ? j - NI * G / 2 : j;
-      const int row = jj * RPI + lane / CPR;    // this lane's row and LDS chunk position
-      const int pos = lane % CPR;
-      const int ch = isv ? pos : (pos ^ (row & (CPR - 1)));  // K: source-side XOR swizzle
-      const uint32_t off = (bi * 64 + row < ctx) ? (uint32_t)((row * D + ch * 8) * 2) : 0x80000000u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(isv ? rv : rk, (da_lds_void*)(dst + (isv ? 64 * D : 0) + jj * 512),
-                                               16, off, 0, 0, 0);
-    }
-  };
-
-  // q stays bf16 (exact: it is the QKV GEMM's bf16 output) for the packed bf16 dot products; the softmax scale
-  // is applied to the f32 score
-  bf16_t* sQb = reinterpret_cast<bf16_t*>(sQ);
-  // first block's DMA before the q prologue: its HBM latency overlaps the q / RoPE-table loads
-  if (blk0 < blk1) stage(0, blk0);
-  const int rpos = fused ? p.positions[b] : 0;
-  // this step's k / v (fused path, last split) loaded now and consumed after the loop, so their latency is hidden
-  const bool new_tok = fused && split == nsp - 1 && p.slots[b] >= 0;
-  // QKV fold fused in: element col of this row = bf16(sum of the kg partial slabs (in slab order, as the fold
-  // adds them) x the folded RMSNorm scale)
-  // This lane's six elements (q halves, k halves, two v) and the row's sum of squares, four slabs per round with
-  // every load issued before the first add (a dependent load-add chain per slab costs ~5 us per layer).
-  const bool part = p.qkv_ws != nullptr;
-  float pv[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (part) {
-    const long pslab = (long)p.B * p.qkv_n;
-    const int lq = lane & (D / 2 - 1), kcol = (p.Hq + hk) * D, vcol = (p.Hq + p.Hkv + hk) * D;
-    const int col[6] = {hq * D + lq, hq * D + lq + D / 2, kcol + lq, kcol + lq + D / 2,
-                        D == 128 ? vcol + 2 * lane : vcol + lane, D == 128 ? vcol + 2 * lane + 1 : vcol + lane};
-    const float* row = p.qkv_ws + (long)b * p.qkv_n;
-    const float* ssr = p.qkv_ws + (long)p.qkv_kg * pslab + b;
-    for (int s0 = 0; s0 < p.qkv_kg; s0 += 4) {
-      float t[4][7];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int sl = min(s0 + u, p.qkv_kg - 1);  // past the last slab: re-read it, dropped below
-#pragma unroll
-        for (int e = 0; e < 6; ++e) t[u][e] = row[(long)sl * pslab + col[e]];
-        t[u][6] = ssr[(long)sl * p.B];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (s0 + u < p.qkv_kg) {
-#pragma unroll
-          for (int e = 0; e < 7; ++e) pv[e] += t[u][e];
-        }
-    }
-    const float rstd = rsqrtf(pv[6] / p.qkv_k + p.qkv_eps);
-#pragma unroll
-    for (int e = 0; e < 6; ++e) pv[e] = bf2f(f2bf(pv[e] * rstd));
-  }
-  float kn0 = 0.f, kn1 = 0.f, kc0 = 0.f, ks0 = 0.f;
-  uint32_t vn_pair = 0u;
-  float vn_one = 0.f;
-  if (new_tok) {
-    const bf16_t* kn = p.knew + (long)b * p.new_bs + (long)hk * D;
-    const bf16_t* vn = p.vnew + (long)b * p.new_bs + (long)hk * D;
-    if (lane < D / 2) {
-      kn0 = part ? pv[2] : bf2f(kn[lane]);
-      kn1 = part ? pv[3] : bf2f(kn[lane + D / 2]);
-      kc0 = p.rope_cos[(long)rpos * (D / 2) + lane];
-      ks0 = p.rope_sin[(long)rpos * (D / 2) + lane];
-    }
-    if constexpr (D == 128) {
-      vn_pair = part ? pack2(pv[4], pv[5])
-                     : *reinterpret_cast<const uint32_t*>(vn + 2 * lane);
-    } else {
-      vn_one = part ? pv[4] : bf2f(vn[lane]);
-    }
-  }
-  if (fused) {  // NeoX RoPE on q (f32 math, bf16 result: what rope_qkv_cache would have stored)
-    const bf16_t* qs = p.q + (long)b * p.q_bs + (long)hq * D;
-    const float* cp = p.rope_cos + (long)rpos * (D / 2);
-    const float* sp = p.rope_sin + (long)rpos * (D / 2);
-    for (int i = lane; i < D / 2; i += 64) {
-      const float x0 = part ? pv[0] : bf2f(qs[i]);  // (i == lane: one pass)
-      const float x1 = part ? pv[1] : bf2f(qs[i + D / 2]);
-      const float c = cp[i], sn = sp[i];
-      sQb[w * D + i] = f2bf(x0 * c - x1 * sn);
-      sQb[w * D + i + D / 2] = f2bf(x1 * c + x0 * sn);
-    }
-  } else {
-    for (int i = lane; i < D; i += 64) sQb[w * D + i] = p.q[(long)b * p.q_bs + (long)hq * D + i];
-  }
-  const float sl2 = p.scale * kLog2e;
-  float m_run = -INFINITY, l_run = 0.f;
-  float o0 = 0.f, o1 = 0.f;  // D=128: this lane's d = 2 lane, 2 lane + 1; D=64: d = lane
-  // (no barrier here: each wave reads only its own sQ row; the loop's barrier publishes the ring)
-  for (int bi = blk0, slot = 0; bi < blk1; ++bi, slot ^= 1) {
-    if (bi + 1 < blk1) {
-      stage(slot ^ 1, bi + 1);
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");  // block bi landed, bi+1 in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    // raw barrier: __syncthreads' fence would drain the ring (vmcnt(0)) and serialise the prefetch
-    __builtin_amdgcn_s_barrier();
-    const bf16_t* sK = ring + slot * SLOT;
-    const bf16_t* sV = sK + 64 * D;
-    // lane = key
-    const int key = bi * 64 + lane;
-    // QK^T: 4 packed bf16 dot products (v_dot2c_f32_bf16) per 8-element chunk, two independent chains
-    float sc0 = 0.f, sc1 = 0.f;
-#pragma unroll
-    for (int ch = 0; ch < CPR; ++ch) {
-      // (pairs taken by shufflevector: bit-casting the elements of a uint32 x4 vector to bf16 x2 miscompiles
-      // with this hipcc -- every pair reads element 0)
-      const bf16x8d kv = __builtin_bit_cast(bf16x8d, *reinterpret_cast<const uint4_*>(sK + lane * D + ((ch ^ (lane & (CPR - 1))) << 3)));
-      const bf16x8d qv = __builtin_bit_cast(bf16x8d, *reinterpret_cast<const uint4_*>(sQb + w * D + ch * 8));
-      sc0 = __builtin_amdgcn_fdot2_f32_bf16(DA_PAIR(kv, 0), DA_PAIR(qv, 0), sc0, false);
-      sc1 = __builtin_amdgcn_fdot2_f32_bf16(DA_PAIR(kv, 1), DA_PAIR(qv, 1), sc1, false);
-      sc0 = __builtin_amdgcn_fdot2_f32_bf16(DA_PAIR(kv, 2), DA_PAIR(qv, 2), sc0, false);
-      sc1 = __builtin_amdgcn_fdot2_f32_bf16(DA_PAIR(kv, 3), DA_PAIR(qv, 3), sc1, false);
-    }
-    float sc = (sc0 + sc1) * sl2;
-    if (key >= ctx) sc = -INFINITY;
-    const float mt = wave_max(sc);
-    const float m_new = fmaxf(m_run, mt);
-    const float alpha = exp2f(m_run - m_new);
-    float e = key < ctx ? exp2f(sc - m_new) : 0.f;
-    o0 *= alpha;
-    o1 *= alpha;
-    if constexpr (D == 128) {
-      // P goes to LDS as bf16 and the denominator sums the same rounded values; P.V runs as packed bf16 dot
-      // products over key pairs: v_perm gathers (V[k][d], V[k+1][d]) for this lane's two dims d
-      const bf16_t eb = f2bf(e);
-      e = bf2f(eb);
-      l_run = l_run * alpha + wave_sum(e);
-      m_run = m_new;
-      bf16_t* sPb = reinterpret_cast<bf16_t*>(sP);
-      sPb[w * 64 + lane] = eb;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's P row is written before it is read
-      float a0 = 0.f, a1 = 0.f;
-#pragma unroll 2
-      for (int k = 0; k < 64; k += 8) {
-        // P[k .. k+7] as 4 bf16 pairs
-        const bf16x8d pk = __builtin_bit_cast(bf16x8d, *reinterpret_cast<const uint4_*>(sPb + w * 64 + k));
-        auto pv = [&](int u, bf16x2d pp, float& c0, float& c1) {
-          const uint32_t va = *reinterpret_cast<const uint32_t*>(sV + (k + 2 * u) * D + 2 * lane);
-          const uint32_t vb = *reinterpret_cast<const uint32_t*>(sV + (k + 2 * u + 1) * D + 2 * lane);
-          const uint32_t lo = __builtin_amdgcn_perm(vb, va, 0x05040100u);  // (V[k][2l],   V[k+1][2l])
-          const uint32_t hi = __builtin_amdgcn_perm(vb, va, 0x07060302u);  // (V[k][2l+1], V[k+1][2l+1])
-          c0 = __builtin_amdgcn_fdot2_f32_bf16(pp, __builtin_bit_cast(bf16x2d, lo), c0, false);
-          c1 = __builtin_amdgcn_fdot2_f32_bf16(pp, __builtin_bit_cast(bf16x2d, hi), c1, false);
-        };
-        pv(0, DA_PAIR(pk, 0), o0, o1);
-        pv(1, DA_PAIR(pk, 1), a0, a1);
-        pv(2, DA_PAIR(pk, 2), o0, o1);
-        pv(3, DA_PAIR(pk, 3), a0, a1);
-      }
-      o0 += a0;
-      o1 += a1;
-    } else {
-      l_run = l_run * alpha + wave_sum(e);
-      m_run = m_new;
-      sP[w * 64 + lane] = e;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's sP row is written before it is read
-#pragma unroll 4
-      for (int k = 0; k < 64; k += 4) {
-        const float4_ pk = *reinterpret_cast<const float4_*>(sP + w * 64 + k);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) o0 += pk[u] * bf2f(sV[(k + u) * D + lane]);
-      }
-    }
-    __builtin_amdgcn_s_barrier();  // every wave is done with this slot before it is refilled (block bi+2)
-  }
-  if (new_tok) {
-    // this step's token: roped k (rounded to bf16, as the cache stores it) and v from the QKV rows, one more
-    // online-softmax key; wave 0 writes both into the cache (no workgroup of this launch reads that row: the
-    // block DMA range-checks it out)
-    const int slot_new = p.slots[b];
-    float kr0 = 0.f, kr1 = 0.f, part = 0.f;
-    if (lane < D / 2) {
-      const float x0 = kn0, x1 = kn1, c = kc0, sn = ks0;
-      kr0 = bf2f(f2bf(x0 * c - x1 * sn));
-      kr1 = bf2f(f2bf(x1 * c + x0 * sn));
-      part = kr0 * bf2f(sQb[w * D + lane]) + kr1 * bf2f(sQb[w * D + lane + D / 2]);
-    }
-    const float sc = wave_sum(part) * sl2;
-    const float m_new = fmaxf(m_run, sc);
-    const float alpha = exp2f(m_run - m_new);
-    float e = exp2f(sc - m_new);
-    if constexpr (D == 128) e = bf2f(f2bf(e));  // P is bf16 on the cache path too
-    l_run = l_run * alpha + e;
-    m_run = m_new;
-    if constexpr (D == 128) {
-      o0 = o0 * alpha + e * bf2f(vn_pair & 0xffff);
-      o1 = o1 * alpha + e * bf2f(vn_pair >> 16);
-    } else {
-      o0 = o0 * alpha + e * vn_one;
-    }
-    if (w == 0) {
-      const long dst = (((long)(slot_new >> 6) * p.Hkv + hk) * 64 + (slot_new & 63)) * D;
-      bf16_t* kc = const_cast<bf16_t*>(p.k_cache);
-      bf16_t* vc = const_cast<bf16_t*>(p.v_cache);
-      if (lane < D / 2) {
-        kc[dst + lane] = f2bf(kr0);
-        kc[dst + lane + D / 2] = f2bf(kr1);
-      }
-      // v from registers (the values attended above; bf16-exact)
-      if constexpr (D == 128) *reinterpret_cast<uint32_t*>(vc + dst + 2 * lane) = vn_pair;
-      else vc[dst + lane] = f2bf(vn_one);
-    }
-  }
-  if (nsp == 1) {  // one split: normalise and write the output here (the combine skips this row)
-    const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-    bf16_t* op = p.o + (long)b * p.o_bs + (long)hq * D;
-    if constexpr (D == 128) {
-      *reinterpret_cast<uint32_t*>(op + 2 * lane) = pack2(o0 * inv, o1 * inv);
-    } else {
-      op[lane] = f2bf(o0 * inv);
-    }
-    return;
-  }
-  // partial results: ws[b][hq][split] = {m, l, o[D]}
-  float* dst = p.ws + (((long)b * p.Hq + hq) * p.num_splits + split) * (D + 2);
-  if (lane == 0) {
-    dst[0] = m_run;
-    dst[1] = l_run;
-  }
-  if constexpr (D == 128) {
-    dst[2 + 2 * lane] = o0;
-    dst[3 + 2 * lane] = o1;
-  } else {
-    dst[2 + lane] = o0;
-  }
-}
-
-// Persistent form: a grid of about two workgroups per CU walks the (sequence, KV head, split) items, split
-// fastest, so one long context's 8 x 64 split items land on 512 different workgroups while the empty items of
-// short sequences (da_splits) cost a ctx_lens read each instead of a workgroup launch with 70 KB of LDS: a
-// batch with one 64k-token sequence launched 16,384 workgroups per layer, 97 % of them empty, and the
-// launch / LDS allocation of the empty ones took longer (1.17 ms per layer) than the attention itself.
-template <int D, int NI>
-__global__ void decode_attn_kernel(const DecodeAttnArgs p) {
-  extern __shared__ __attribute__((aligned(16))) char dsm[];
-  const int total = p.B * p.Hkv * p.num_splits;
-  const int S = p.num_splits;
-  const bool rotate = (int)gridDim.x < total;  // persistent walk only (one workgroup per item needs no spreading)
-  for (int item = blockIdx.x; item < total; item += gridDim.x) {
-    // a sequence's splits sit at slots rotated by b: a short sequence's one real item lands on slot b % S instead
-    // of slot 0, so the short sequences' items spread over the grid instead of piling onto the few workgroups
-    // whose stride hits slot 0 (measured: 16 short sequences beside a 128k one made the launch 2.7x slower)
-    const int sidx = item % S, r = item / S;
-    const int b = r / p.Hkv, hk = r - b * p.Hkv;
-    const int split = rotate ? (sidx - b % S + S) % S : sidx;
-    decode_attn_item<D, NI>(p, dsm, b, hk, split);
-    __syncthreads();  // the next item restages ring slot 0
-  }
-}
-
 __global__ void decode_combine_kernel(const DecodeAttnArgs p) {
   const int b = blockIdx.x, hq = blockIdx.y;
   const int D = p.D;
@@ -972,10 +661,10 @@ __global__ void __launch_bounds__(kWbG * 64, 2) decode_attn_wb_kernel(const Deco
   uint4_ vr[16];
   // descriptor sized to the block's rows inside the context: rows past it read as zeros (the range check of the
   // buffer instruction), so the offsets carry no per-lane select and fold into base + immediate / SGPR offsets
-  auto rsrc = [&](const bf16_t* cache, int phys, int bi) {
+  auto rsrc = [&](const void* cache, int phys, int bi) {
     const int rows = min(64, ctx - bi * 64);
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(cache + ((long)phys * p.Hkv + hk) * 64 * D),
-                                             (short)0, rows * D * 2, 0x00020000);
+    const bf16_t* blk = static_cast<const bf16_t*>(cache) + ((long)phys * p.Hkv + hk) * 64 * D;
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(blk), (short)0, rows * D * 2, 0x00020000);
   };
   // K: instruction t fills rows 4t .. 4t + 3 lane-linearly; LDS position lpos of row r holds global chunk
   // lpos ^ (r & 15), and (4t + lrow) & 15 repeats with t % 4
@@ -1203,8 +892,8 @@ __global__ void __launch_bounds__(kWbG * 64, 2) decode_attn_wb_kernel(const Deco
     if (w == 0) {  // this step's k / v into the cache (no workgroup of this launch reads that row)
       const int slot_new = p.slots[b];
       const long dst = (((long)(slot_new >> 6) * p.Hkv + hk) * 64 + (slot_new & 63)) * D;
-      bf16_t* kc = const_cast<bf16_t*>(p.k_cache);
-      bf16_t* vc = const_cast<bf16_t*>(p.v_cache);
+      bf16_t* kc = static_cast<bf16_t*>(const_cast<void*>(p.k_cache));
+      bf16_t* vc = static_cast<bf16_t*>(const_cast<void*>(p.v_cache));
       kc[dst + lane] = f2bf(kr0);
       kc[dst + lane + D / 2] = f2bf(kr1);
       *reinterpret_cast<uint32_t*>(vc + dst + 2 * lane) = vn_pair;
@@ -1212,11 +901,6 @@ __global__ void __launch_bounds__(kWbG * 64, 2) decode_attn_wb_kernel(const Deco
   }
   const float inv = L > 0.f ? 1.f / L : 0.f;
   *reinterpret_cast<uint32_t*>(p.o + (long)b * p.o_bs + (long)hq * D + 2 * lane) = pack2(o0 * inv, o1 * inv);
-}
-
-// the split combine for launchers in other translation units (attention_kv8.hip: same partial format)
-void launch_decode_combine(const DecodeAttnArgs& a, hipStream_t s) {
-  decode_combine_kernel<<<dim3(a.B, a.Hq), 128, 0, s>>>(a);
 }
 
 static int g_decode_wb = -1;
@@ -1237,13 +921,31 @@ size_t decode_attn_workspace(int B, int Hq, int D, int num_splits) {
   return (size_t)B * Hq * num_splits * (D + 2) * sizeof(float);
 }
 
+// the split kernel's launch for one format and head dim: NI = wave DMA instructions per block per wave =
+// (2 * 64 * D * element bytes / 1024) / G
+template <template <int> class Fmt, int D>
+static void launch_decode_split(const DecodeAttnArgs& a, dim3 grid, int G, hipStream_t s) {
+  constexpr int NB = 2 * 64 * D * (int)sizeof(typename Fmt<D>::E) / 1024;
+  const size_t lds = (size_t)NB * 2 * 1024 + Fmt<D>::kQBytes + 8 * 64 * 4;  // two ring slots, q rows, P rows
+#define DA(G_) decode_attn_kernel<Fmt<D>, D, NB / G_><<<grid, G_ * 64, lds, s>>>(a)
+  switch (G) {
+    case 1: DA(1); break;
+    case 2: DA(2); break;
+    case 4: DA(4); break;
+    case 8: DA(8); break;
+    default: break;  // (the bindings reject other groups: NI * G must be the block's instruction count)
+  }
+#undef DA
+}
+
 void launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
   const int G = a.Hq / a.Hkv;
-  if (a.D == 128 && G == kWbG && a.num_splits == 1 && decode_wb_mode()) {  // wave-per-block short-context kernel
+  // wave-per-block short-context kernel (bf16 cache only: an fp8 cache always takes the split kernel)
+  if (!a.kv_fp8 && a.D == 128 && G == kWbG && a.num_splits == 1 && decode_wb_mode()) {
     decode_attn_wb_kernel<<<dim3((unsigned)(a.B * a.Hkv)), kWbG * 64, kWbLds, s>>>(a);
     return;
   }
-  static const int width = [] {  // two workgroups per CU (70 KB of LDS each)
+  static const int width = [] {  // two workgroups per CU (70 KB of LDS each at bf16, D = 128)
     int dev = 0, cus = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
@@ -1258,26 +960,14 @@ void launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
   }();
   const long items = (long)a.B * a.Hkv * a.num_splits;
   const bool persist = force >= 0 ? force == 1 : a.num_splits > 8;
-  dim3 grid((unsigned)(persist ? std::min<long>(items, width) : items));
-  const size_t lds = (size_t)4 * 64 * a.D * sizeof(bf16_t) + (size_t)8 * a.D * 4 + 8 * 64 * 4;
-  // NI = wave DMA instructions per block per wave = (2 * 64 * D * 2 / 1024) / G
-#define DA(D_, NI_) decode_attn_kernel<D_, NI_><<<grid, G * 64, lds, s>>>(a)
-  if (a.D == 128) {
-    switch (G) {
-      case 1: DA(128, 32); break;
-      case 2: DA(128, 16); break;
-      case 4: DA(128, 8); break;
-      default: DA(128, 4); break;  // G = 8
-    }
+  const dim3 grid((unsigned)(persist ? std::min<long>(items, width) : items));
+  if (a.kv_fp8) {
+    if (a.D == 128) launch_decode_split<KvFp8, 128>(a, grid, G, s);
+    else launch_decode_split<KvFp8, 64>(a, grid, G, s);
   } else {
-    switch (G) {
-      case 1: DA(64, 16); break;
-      case 2: DA(64, 8); break;
-      case 4: DA(64, 4); break;
-      default: DA(64, 2); break;
-    }
+    if (a.D == 128) launch_decode_split<KvBf16, 128>(a, grid, G, s);
+    else launch_decode_split<KvBf16, 64>(a, grid, G, s);
   }
-#undef DA
   if (a.num_splits > 1) decode_combine_kernel<<<dim3(a.B, a.Hq), 128, 0, s>>>(a);
 }
 

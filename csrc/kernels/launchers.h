@@ -279,8 +279,8 @@ void launch_attn512(const AttnArgs& a, hipStream_t s);
 
 struct DecodeAttnArgs {
   const bf16_t* q;          // [B, Hq, D]
-  const bf16_t* k_cache;    // [num_blocks, Hkv, 64, D]
-  const bf16_t* v_cache;
+  const void* k_cache;      // [num_blocks, Hkv, 64, D], bf16 or (kv_fp8) one-byte e4m3 codes
+  const void* v_cache;
   bf16_t* o;                // [B, Hq, D]
   const int* block_table;   // [B, max_blocks]
   const int* ctx_lens;      // [B]
@@ -288,6 +288,8 @@ struct DecodeAttnArgs {
   int B, Hq, Hkv, D, max_blocks, num_splits;
   long q_bs, o_bs;
   float scale;
+  bool kv_fp8;              // the caches hold fp8 codes (see k_scale below): split kernel only.  (In the padding
+                            // behind scale: the kernels' argument layout is what it was without the field)
   // fused decode step (knew != nullptr): q is un-roped; this step's k / v rows ([B, Hkv, D] at row stride
   // new_bs) are roped / taken from here, written into the cache at slots[b] (-1: padding row) and attended
   // from registers; ctx_lens count the new token, the cache holds ctx_lens - 1 of them
@@ -304,16 +306,14 @@ struct DecodeAttnArgs {
   const float* qkv_ws;
   int qkv_kg, qkv_n, qkv_k;
   float qkv_eps;
-  // fp8 (OCP e4m3fn) cache (launch_decode_attn_kv8 only; k_cache / v_cache then point at bytes): stored code =
-  // fp8(clamp(x * k_inv, +-448)), value = float(code) * k_scale; k_inv = 1 / k_scale computed on the host
+  // fp8 (OCP e4m3fn) cache (kv_fp8): stored code = fp8(clamp(x * k_inv, +-448)), value = float(code) * k_scale;
+  // k_inv = 1 / k_scale computed on the host
   float k_scale, v_scale, k_inv, v_inv;
 };
+// Hq / Hkv must be 1, 2, 4 or 8.  A bf16 cache takes the split kernel (decode_common.h) or, for short contexts, the
+// wave-per-block kernel; an fp8 cache always the split kernel (there is no wave-per-block form)
 void launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s);
-// the split combine alone (partials ws[b][hq][split] = {m, l, o[D]} -> o), shared by both cache dtypes
-void launch_decode_combine(const DecodeAttnArgs& a, hipStream_t s);
-// fp8 KV cache (attention_kv8.hip): the split decode kernel over byte caches (always the split kernel: there is no
-// wave-per-block form), the cache writers, and the block widener that feeds the bf16 prefill kernels
-void launch_decode_attn_kv8(const DecodeAttnArgs& a, hipStream_t s);
+// fp8 KV cache (attention_kv8.hip): the cache writers, and the block widener that feeds the bf16 prefill kernels
 void launch_kv_write_f8(const bf16_t* k, const bf16_t* v, uint8_t* k_cache, uint8_t* v_cache, const int* slot_mapping,
                         int T, int Hkv, int D, long k_ts, long v_ts, float k_inv, float v_inv, hipStream_t s);
 void launch_rope_qkv_cache_f8(bf16_t* qkv, long ld, const int* pos, const float* cos, const float* sin,

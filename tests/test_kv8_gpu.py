@@ -148,6 +148,51 @@ def test_decode_attn_fp8(cuda, D, Hq, Hkv, long_ctx):
         close(o, want, 2e-2)
 
 
+@pytest.mark.parametrize("D,Hq,Hkv", [(128, 8, 8), (128, 16, 8), (128, 32, 8), (128, 64, 8), (64, 8, 8), (64, 16, 4)])
+def test_split_decode_formats_agree(cuda, D, Hq, Hkv):
+    """The split kernel is one body for both cache formats: over a bf16 cache whose every value is an e4m3 value and
+    its fp8 twin (scales 1.0) the two formats do the same arithmetic in the same order -- widening a code to bf16 is
+    exact -- so the outputs are equal bit for bit, and both meet the fp32 reference.  Every GQA group at D = 128 and
+    two at D = 64; contexts around the 64-token block edge and up to 10 blocks (1 to 3 splits per sequence); 9
+    splits at Hkv = 8 are 576 items, more than two per CU: the persistent walk with split rotation."""
+    torch.manual_seed(23)
+    ctx = [1, 63, 64, 65, 300, 520, 580, 600]
+    B = len(ctx)
+    k8, v8, bt = _paged_setup8(B, Hkv, D, ctx, sum((c + 63) // 64 for c in ctx) + 8, 1.0, 1.0)
+    kb, vb = ops.dequant_kv_fp8(k8, 1.0, torch.bfloat16), ops.dequant_kv_fp8(v8, 1.0, torch.bfloat16)
+    assert torch.equal(_u8(ops.quantize_kv_fp8(kb, 1.0)), _u8(k8))   # the bf16 cache holds the codes' values exactly
+    q = rnd(B, Hq, D)
+    lens = torch.tensor(ctx, dtype=torch.int32, device="cuda")
+    want = ref.decode_attention(q, kb.float(), vb.float(), bt, lens, 1 / math.sqrt(D))
+    prev = ops.set_decode_wb(-1)
+    try:
+        ops.set_decode_wb(0)   # D 128, group 4, one split: the bf16 cache takes the split kernel too
+        for splits in (1, 3, 9):
+            o8 = ops.decode_attention(q, k8, v8, bt, lens, num_splits=splits, k_scale=1.0, v_scale=1.0)
+            ob = ops.decode_attention(q, kb, vb, bt, lens, num_splits=splits)
+            close(o8, want, 2e-2)
+            close(ob, want, 2e-2)
+            diff = (o8.float() - ob.float()).abs()
+            print(f"splits {splits}: fp8 vs bf16 cache: {int((o8 != ob).sum())} of {o8.numel()} elements differ, "
+                  f"max |diff| {diff.max().item():.3g}")
+            assert torch.equal(o8, ob)
+    finally:
+        ops.set_decode_wb(prev)
+
+
+def test_decode_attention_rejects_unsupported_gqa_group(cuda):
+    """The split kernel has instantiations for GQA groups 1, 2, 4 and 8; any other group (here 24 / 8 = 3) is
+    rejected by the binding before a launch, for both cache formats."""
+    D, Hq, Hkv = 128, 24, 8
+    q = rnd(1, Hq, D)
+    bt = torch.zeros(1, 1, dtype=torch.int32, device="cuda")
+    lens = torch.ones(1, dtype=torch.int32, device="cuda")
+    for dtype in (torch.bfloat16, F8):
+        kc = torch.zeros(2, Hkv, 64, D, dtype=dtype, device="cuda")
+        with pytest.raises(RuntimeError, match="1, 2, 4 and 8"):
+            ops.decode_attention(q, kc, torch.zeros_like(kc), bt, lens)
+
+
 @pytest.mark.parametrize("wb", [0, 1])
 @pytest.mark.parametrize("source", ["qkv_rows", "partial_slabs"])
 def test_decode_attn_fp8_fused(cuda, wb, source):
