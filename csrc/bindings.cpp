@@ -185,6 +185,12 @@ constexpr int kSkinny2Cfg = 1200;
 constexpr int kSkinny2DeepCfg = 1250;
 inline bool is_skinny2(int cfg) { return cfg == kSkinny2Cfg || cfg == kSkinny2DeepCfg; }
 inline bool is_skinny(int cfg) { return cfg == kSkinnyCfg || cfg == kSkinnyFixCfg || is_skinny2(cfg); }
+// Choice.cfg of the MXFP4 tile GEMM (csrc/kernels/gemm_fp4.hip, M > 64): kFp4TileCfg + 32 * tile; Choice.splits = its
+// split-K count.  A forced number is kFp4TileCfg + 32 * tile + splits (splits 1..16, 0 = the heuristic count).
+constexpr int kFp4TileCfg = 1300;
+inline bool is_fp4_tile(int cfg) {
+  return cfg >= kFp4TileCfg && cfg < kFp4TileCfg + 32 * shai::gemm_fp4_num_tiles() && (cfg - kFp4TileCfg) % 32 == 0;
+}
 
 // Last resort when neither the tuner nor the planner produced a usable config: an explicit, directly tested
 // config, never "whichever kernel happens to be numbered highest".  The v2 128x64 tile (cfg 4) runs every
@@ -213,8 +219,8 @@ void launch_skinny2_choice(const shai::GemmArgs& g, const Tensor& like, int kg, 
   shai::launch_skinny2(g, wsp, kg, deep, stream());
 }
 
-// MXFP4 weights (csrc/kernels/gemv_fp4.hip): the only kernel of such a problem.  Its choices reuse kSkinnyCfg (split-K
-// with the separate fold) and kSkinnyFixCfg (in-launch fixup) under the problem's own "|mxfp4w" key.
+// MXFP4 weights at M <= 64 (csrc/kernels/gemv_fp4.hip): the only kernel of such a problem.  Its choices reuse
+// kSkinnyCfg (split-K with the separate fold) and kSkinnyFixCfg (in-launch fixup) under the problem's own "|mxfp4w" key.
 void launch_skinny_fp4_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
   Tensor ws;
   float* wsp = nullptr;
@@ -224,6 +230,24 @@ void launch_skinny_fp4_choice(const shai::GemmArgs& g, const Tensor& like, int k
     wsp = ws.data_ptr<float>();
   }
   shai::launch_skinny_fp4(g, wsp, kg, fixup, stream());
+}
+
+// MXFP4 weights at M > 64 (csrc/kernels/gemm_fp4.hip): tile config x split count, the workspace allocated as the
+// skinny choices allocate theirs (caching allocator: safe under graph capture)
+void launch_fp4_tile_choice(const shai::GemmArgs& g, const Tensor& like, int tile, int splits) {
+  Tensor ws;
+  float* wsp = nullptr;
+  const size_t bytes = shai::gemm_fp4_workspace_bytes(g, splits);
+  if (bytes > 0) {
+    ws = at::empty({(long)(bytes / sizeof(float))}, like.options().dtype(at::kFloat));
+    wsp = ws.data_ptr<float>();
+  }
+  shai::launch_gemm_fp4(g, wsp, tile, splits, stream());
+}
+
+Choice fp4_tile_default(const shai::GemmArgs& g) {
+  const int tile = shai::gemm_fp4_tile(g);
+  return Choice{kFp4TileCfg + 32 * tile, shai::gemm_fp4_splits(g, tile)};
 }
 
 void launch_skinny_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
@@ -260,6 +284,12 @@ void launch_lib(const shai::GemmArgs& g, const Tensor& like) {
 
 void launch_choice(const shai::GemmArgs& g, const Tensor& like, Choice c) {
   if (g.w_mx_scale != nullptr) {
+    if (g.M > 64) {
+      SHAI_CHECK(shai::gemm_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 tile kernel");
+      if (!is_fp4_tile(c.cfg)) c = fp4_tile_default(g);  // a choice of another kernel filed under this key
+      launch_fp4_tile_choice(g, like, (c.cfg - kFp4TileCfg) / 32, c.splits);
+      return;
+    }
     SHAI_CHECK(shai::skinny_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 skinny kernel");
     launch_skinny_fp4_choice(g, like, c.splits, c.cfg == kSkinnyFixCfg);
     return;
@@ -326,7 +356,12 @@ Choice tune(const shai::GemmArgs& g_real, const Tensor& like, bool skinny_only =
   g.batch_c = (long)g.M * n_out;
   Choice def{kSkinnyCfg, g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g)};
   std::vector<Choice> cands;
-  if (g.w_mx_scale != nullptr) {
+  if (g.w_mx_scale != nullptr && g.M > 64) {  // the fp4 tile kernel: every tile config x split count
+    skinny_only = true;
+    def = fp4_tile_default(g);
+    for (int t = 0; t < shai::gemm_fp4_num_tiles(); ++t)
+      for (int sp = 1; sp <= shai::gemm_fp4_max_splits(g); sp *= 2) cands.push_back({kFp4TileCfg + 32 * t, sp});
+  } else if (g.w_mx_scale != nullptr) {
     skinny_only = true;
     for (int kg = 1; kg <= shai::skinny_fp4_max_kgroups(g); kg *= 2) {
       cands.push_back({kSkinnyCfg, kg});
@@ -408,6 +443,23 @@ void run_skinny(const shai::GemmArgs& g, const Tensor& like) {
       store_choice(g, key, c);
     } else {
       c = Choice{kSkinnyCfg, g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g)};
+    }
+  }
+  launch_choice(g, like, c);
+}
+
+// MXFP4 problems of more than 64 rows: tuned over the fp4 tile kernel's configs x split counts (exact key, then the
+// row-count bucket, as the bf16 prefill GEMMs); the heuristic choice under graph capture or with the tuner off.
+void run_fp4_tile(const shai::GemmArgs& g, const Tensor& like) {
+  const std::string key = gemm_key(g);
+  Choice c{-1, 1};
+  if (!lookup_choice(g, key, &c) || !is_fp4_tile(c.cfg)) c = Choice{-1, 1};
+  if (c.cfg < 0) {
+    if (!stream_capturing() && autotune_enabled()) {
+      c = tune(g, like, true);
+      store_choice(g, key, c);
+    } else {
+      c = fp4_tile_default(g);
     }
   }
   launch_choice(g, like, c);
@@ -516,6 +568,11 @@ std::vector<std::string> gemm_tuning_table() {
     }
     if (kv.second.cfg == kLibCfg) {
       out.push_back(kv.first + " -> hipblaslt");
+      continue;
+    }
+    if (is_fp4_tile(kv.second.cfg)) {
+      out.push_back(kv.first + " -> fp4 tile " + std::to_string((kv.second.cfg - kFp4TileCfg) / 32) + " splitk=" +
+                    std::to_string(kv.second.splits));
       continue;
     }
     int bm, bn;
@@ -822,15 +879,18 @@ void attach_norm_io(shai::GemmArgs& g, const optional<Tensor>& ln_mr, const opti
 }
 
 // MXFP4 weights (ops.quantize_mxfp4): w float4_e2m1fn_x2 [N, K / 2] (two codes per byte), w_scale e8m0 bytes tiled per
-// 128-wide K step, [ceil(K / 128), N, 4]; decode-shaped activations a [M <= 64, K] only (larger problems dequantise).
-// force_cfg (tests / tools; < 0: tuned per shape): 1000 = the heuristic K-group count with the separate fold,
+// 128-wide K step, [ceil(K / 128), N, 4].  Activations a [M, K] of M <= 64 rows run on the skinny kernel
+// (gemv_fp4.hip), more rows on the tile kernel (gemm_fp4.hip; a folded RMSNorm runs as an explicit row-norm pass first).
+// force_cfg (tests / tools; < 0: tuned per shape), M <= 64: 1000 = the heuristic K-group count with the separate fold,
 // 1000 + kg = kg K groups folded by the separate kernel (1001 = no split), 1100 + kg = kg K groups fixed up inside
-// the launch -- the numbers of the bf16 / fp8 skinny kernel, here always on gemv_fp4.hip (1 <= kg <= 64).
+// the launch -- the numbers of the bf16 / fp8 skinny kernel, here always on gemv_fp4.hip (1 <= kg <= 64).  M > 64:
+// 1300 + 32 * tile + splits (tile 0 = 128 x 128, 1 = 256 x 128; splits 1..16, 0 = the heuristic count).  A number
+// of the other row range is a "bad force_cfg" error.
 void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
                 const optional<Tensor>& residual, double alpha, double res_alpha, int64_t act, bool glu,
                 int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale) {
-  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(0) <= 64 && a.size(1) >= 32 && a.size(1) % 32 == 0,
-             "mxfp4 gemm: decode-shaped activations only (1 <= M <= 64, K % 32 == 0); dequantize for larger M");
+  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(1) >= 32 && a.size(1) % 32 == 0,
+             "mxfp4 gemm: a must be a 2-D activation [M >= 1, K] with K % 32 == 0");
   const long M = a.size(0), K = a.size(1);
   SHAI_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() && w.size(1) * 2 == K &&
                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
@@ -874,6 +934,32 @@ void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optiona
   g.res_alpha = res_alpha;
   g.act = act;
   g.glu = glu;
+  if (M > 64) {  // the tile kernel
+    const int ft = (int)(force_cfg - kFp4TileCfg) / 32, fs = (int)(force_cfg - kFp4TileCfg) % 32;
+    SHAI_CHECK(force_cfg < 0 || (force_cfg >= kFp4TileCfg && ft < shai::gemm_fp4_num_tiles() && fs <= 16),
+               "mxfp4 gemm: bad force_cfg ", force_cfg, " for M = ", M,
+               " > 64: 1300 + 32 * tile + splits (tile 0..", shai::gemm_fp4_num_tiles() - 1, ", splits 0..16)");
+    Tensor xn;
+    if (rms_eps >= 0) {  // folded RMSNorm above 64 rows: the explicit unweighted pass, as on the bf16 tile kernels
+      SHAI_CHECK(K % 8 == 0 && K <= 8192, "folded RMSNorm: K must be a multiple of 8 and <= 8192");
+      xn = at::empty({M, K}, a.options());
+      shai::RowNormArgs r{};
+      r.x = cptr(a);
+      r.out = mptr(xn);
+      r.rows = g.M;
+      r.D = g.K;
+      r.x_stride = g.lda;
+      r.out_stride = g.K;
+      r.eps = rms_eps;
+      shai::launch_rmsnorm(r, stream());
+      g.A = cptr(xn);
+      g.lda = K;
+    }
+    SHAI_CHECK(shai::gemm_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 tile kernel");
+    if (force_cfg >= 0) launch_choice(g, a, Choice{kFp4TileCfg + 32 * ft, fs > 0 ? fs : shai::gemm_fp4_splits(g, ft)});
+    else run_fp4_tile(g, a);
+    return;
+  }
   if (rms_eps >= 0) {
     g.rms = 1;
     g.rms_eps = (float)rms_eps;
@@ -881,7 +967,7 @@ void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optiona
   SHAI_CHECK(shai::skinny_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 skinny kernel");
   SHAI_CHECK(force_cfg < 0 || (force_cfg >= kSkinnyCfg && force_cfg <= kSkinnyCfg + 64) ||
                  (force_cfg > kSkinnyFixCfg && force_cfg <= kSkinnyFixCfg + 64),
-             "mxfp4 gemm: force_cfg must be 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
+             "mxfp4 gemm: bad force_cfg ", force_cfg, " for M = ", M, " <= 64: 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
   if (force_cfg > kSkinnyFixCfg) launch_choice(g, a, Choice{kSkinnyFixCfg, (int)(force_cfg - kSkinnyFixCfg)});
   else if (force_cfg > kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, (int)(force_cfg - kSkinnyCfg)});
   else if (force_cfg == kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, shai::skinny_fp4_kgroups(g)});
@@ -1682,7 +1768,7 @@ int64_t gemm_tuning_import(const std::vector<std::string>& entries) {
     if (eq == std::string::npos || cm == std::string::npos || cm < eq) continue;
     const int cfg = atoi(e.substr(eq + 1, cm - eq - 1).c_str());
     const int sp = atoi(e.substr(cm + 1).c_str());
-    if ((cfg < 0 || cfg >= shai::gemm2_num_cfgs()) && !is_skinny(cfg) && cfg != kLibCfg) continue;
+    if ((cfg < 0 || cfg >= shai::gemm2_num_cfgs()) && !is_skinny(cfg) && !is_fp4_tile(cfg) && cfg != kLibCfg) continue;
     if (cfg == kLibCfg && !lib_enabled()) continue;
     if (sp < 1) continue;
     g_tuned[e.substr(0, eq)] = Choice{cfg, sp};

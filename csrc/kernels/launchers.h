@@ -130,8 +130,9 @@ struct GemmArgs {
   float rms_eps;
   // fp8 weights (skinny kernel only): W is e4m3 [N, K] bytes, w_scale[n] fp32 per output row
   const float* w_scale;
-  // MXFP4 weights (gemv_fp4.hip only): W is e2m1 codes [N, K / 2] bytes (ldw in BYTES), w_mx_scale the e8m0 group
-  // scales tiled per 128-wide K step, [ceil(K / 128), N, 4] bytes.  Every other kernel rejects such a problem.
+  // MXFP4 weights (gemv_fp4.hip for M <= 64, gemm_fp4.hip above): W is e2m1 codes [N, K / 2] bytes (ldw in BYTES),
+  // w_mx_scale the e8m0 group scales tiled per 128-wide K step, [ceil(K / 128), N, 4] bytes.  Every other kernel
+  // rejects such a problem.
   const uint8_t* w_mx_scale;
   int w_nt;                 // skinny kernel: weight stream with the nt cache policy (set by its launcher)
   // LayerNorm folded into the GEMM (v4 kernel, unsplit, batch 1): acc <- rstd[m] * (acc - mean[m] * col_s[n])
@@ -157,7 +158,7 @@ inline bool tile_act_supported(const GemmArgs& a) {
   if (a.glu) return a.act == 1 || a.act == 2 || a.act == 3;      // ACT_SILU, ACT_GELU, ACT_GELU_TANH
   return true;
 }
-// the weights are not plain bf16 (fp8 rows or MXFP4): only the skinny kernel written for the format takes them
+// the weights are not plain bf16 (fp8 rows or MXFP4): only the kernels written for the format take them
 inline bool quantized_w(const GemmArgs& a) { return a.w_scale != nullptr || a.w_mx_scale != nullptr; }
 void launch_dequant_fp8_rows(const uint8_t* w8, const float* scale, bf16_t* out, long N, int K, hipStream_t s);
 // fp8 e4m3 MFMA GEMM (gemm_f8.hip): C = epi(a_scale[m] w_scale[n] A8 W8^T); A8 / W8 are e4m3 bytes, lda / ldw in
@@ -231,6 +232,16 @@ int skinny_fp4_kgroups(const GemmArgs& a);       // heuristic K-group count
 int skinny_fp4_max_kgroups(const GemmArgs& a);   // largest K-group count worth trying (autotuner)
 size_t skinny_fp4_workspace_bytes(const GemmArgs& a, int kg);
 void launch_skinny_fp4(const GemmArgs& a, float* ws, int kg, bool fixup, hipStream_t s);
+// MXFP4 tile GEMM (gemm_fp4.hip): M > 64, GemmArgs::w_mx_scale set, bf16 MFMA on codes widened in registers; bias /
+// activation / GLU / residual epilogues (no folded RMSNorm: the caller normalises the rows first).  tile 0 = 128 x 128,
+// 1 = 256 x 128; split-K over `splits` K groups (ws of gemm_fp4_workspace_bytes) folded by launch_splitk_epilogue
+bool gemm_fp4_supported(const GemmArgs& a);
+int gemm_fp4_num_tiles();
+int gemm_fp4_tile(const GemmArgs& a);               // heuristic tile config
+int gemm_fp4_splits(const GemmArgs& a, int tile);   // heuristic split count of that tile
+int gemm_fp4_max_splits(const GemmArgs& a);         // largest split count worth trying (autotuner)
+size_t gemm_fp4_workspace_bytes(const GemmArgs& a, int splits);
+void launch_gemm_fp4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s);
 // MXFP4 codes [N, K / 2] + tiled scales [ceil(K / 128), N, 4] -> bf16 [N, K] (K % 32 == 0)
 void launch_dequant_mxfp4(const uint8_t* wq, const uint8_t* scales, bf16_t* out, long N, int K, hipStream_t s);
 

@@ -157,8 +157,10 @@ def dequant_fp8(w8: torch.Tensor, scale: torch.Tensor, dtype=torch.bfloat16) -> 
 
 
 # ---- MXFP4 weight-only quantisation (``quantize_mxfp4``: a load-time transform in pure torch, CPU and GPU; format and
-# layout in ops/reference.py).  Decode-shaped GEMMs stream the packed codes (csrc/kernels/gemv_fp4.hip); anything else
-# dequantises to bf16 first (as FP8_PREFILL="dequant" does) -- a fused MX-scaled MFMA prefill GEMM is the follow-up.
+# layout in ops/reference.py).  GEMMs stream the packed codes: <= 64 rows through the skinny kernel
+# (csrc/kernels/gemv_fp4.hip), more rows through the tile kernel (csrc/kernels/gemm_fp4.hip: codes widened to bf16 in
+# registers, bf16 MFMA -- weight-only and exact).  Gated / LayerNorm-folded / batched calls and the CPU dequantise to
+# bf16 first.  An MX-scaled MFMA (W4A8: quantised activations, other numbers) would be a separate opt-in.
 def is_mxfp4(w: torch.Tensor) -> bool:
     return w.dtype == torch.float4_e2m1fn_x2
 
@@ -172,17 +174,30 @@ def dequant_mxfp4(wq: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) 
     return out if dtype == torch.bfloat16 else out.to(dtype)
 
 
+# MXFP4 weights on problems of more than 64 rows (prefill, decode above 64 sequences): "fused" streams the packed codes
+# through the fp4 tile GEMM (gemm_fp4.hip); "dequant" widens the whole matrix to bf16 per call and runs the bf16 GEMMs
+MXFP4_PREFILL = os.environ.get("SHAI_MXFP4_PREFILL", "fused")
+# largest row count the fused route takes (0: no cap): the largest measured M at which it is not slower than the
+# dequantise route at any Mistral-7B / 70B projection shape (table in profiles/mxfp4_prefill.md: it wins 1.1-3.6x up
+# to 768 rows, loses at one shape at 1024 and at every shape at 4096, where the four-wave bf16 GEMM outruns it)
+MXFP4_FUSED_MAX_ROWS = int(os.environ.get("SHAI_MXFP4_FUSED_MAX_ROWS", "768"))
+
+
 def _mxfp4_route(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor], direct_ok: bool = True):
-    """(w, w_scale) for a GEMM of ``x`` against MXFP4 weights: the packed pair where the fp4 skinny kernel takes the
-    problem (GPU, <= 64 rows, K % 32 == 0), else the dequantised bf16 matrix."""
+    """(w, w_scale) for a GEMM of ``x`` against MXFP4 weights: the packed pair where an fp4 kernel takes the problem
+    (GPU, K % 32 == 0; <= 64 rows: the skinny kernel; more rows: the tile kernel, unless ``MXFP4_PREFILL`` is
+    "dequant" or the row count is above ``MXFP4_FUSED_MAX_ROWS``), else the dequantised bf16 matrix."""
     if w_scale is None:
         raise ValueError("MXFP4 weights need w_scale= (the group scales of quantize_mxfp4)")
     K = x.shape[-1]
     if w.shape[1] * 2 != K:
         raise ValueError(f"MXFP4 weight {tuple(w.shape)} holds K = {w.shape[1] * 2}, the activation has K = {K}")
     M = x.numel() // K
-    if direct_ok and _gpu(x) and 1 <= M <= 64 and K % 32 == 0:
-        return w, w_scale
+    if direct_ok and _gpu(x) and M >= 1 and K % 32 == 0:
+        # (N % 4: the tile kernel wants whole column quads under GLU; such widths kept the dequantise route)
+        if M <= 64 or (MXFP4_PREFILL == "fused" and w.shape[0] % 4 == 0
+                       and (MXFP4_FUSED_MAX_ROWS <= 0 or M <= MXFP4_FUSED_MAX_ROWS)):
+            return w, w_scale
     return dequant_mxfp4(w, w_scale), None
 
 
@@ -236,8 +251,11 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     problems (<= 64 rows) stream the fp8 bytes through the skinny kernel (half the weight
     traffic); larger ones run W8A8 on the fp8 MFMA (``FP8_PREFILL``: the activation is quantised per row, with
     the folded RMSNorm in its row scale) or dequantize to bf16 first and run the bf16 GEMMs.
-    ``w`` of dtype float4_e2m1fn_x2 is MXFP4 (``quantize_mxfp4``; ``w_scale`` its e8m0 group scales): <= 64 rows on
-    the GPU stream the packed codes through the fp4 skinny kernel, everything else dequantises to bf16 first.
+    ``w`` of dtype float4_e2m1fn_x2 is MXFP4 (``quantize_mxfp4``; ``w_scale`` its e8m0 group scales): on the GPU the
+    packed codes stream through the fp4 skinny kernel (<= 64 rows) or the fp4 tile GEMM (more rows, up to
+    ``MXFP4_FUSED_MAX_ROWS``; ``MXFP4_PREFILL``); larger problems, a ``row_affine`` call and the CPU dequantise to bf16
+    first.  force_cfg (tests / tools) then
+    names an fp4 config: 1000 (+ kg) / 1100 + kg at <= 64 rows, 1300 + 32 * tile + splits above.
     """
     if is_mxfp4(w):
         w, w_scale = _mxfp4_route(x, w, w_scale, direct_ok=row_affine is None)
@@ -426,8 +444,8 @@ def gemm_into(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias=None, ac
     """out = gate[row // rows_per_gate] * act(alpha * x @ w^T + bias) + res_alpha * residual, written into ``out``.
     rms_eps >= 0: x is RMS-normalised first (unweighted; fold the gain into w).
     w_scale: fp8 e4m3 ``w`` with per-row scales (skinny kernel only, as in ``linear``), or the group scales of an
-    MXFP4 ``w`` (2-D x of <= 64 rows without a gate: the fp4 skinny kernel, force_cfg 1000 (+ kg) / 1100 + kg as
-    below; anything else dequantises first).
+    MXFP4 ``w`` (2-D x without a gate: the fp4 skinny kernel at <= 64 rows, force_cfg 1000 (+ kg) / 1100 + kg as
+    below, the fp4 tile GEMM above, force_cfg 1300 + 32 * tile + splits; anything else dequantises first).
     force_cfg (tests / tools): a tile config index, 1000 (+ kg) = skinny kernel with a separate split-K fold,
     1100 + kg = skinny kernel reducing its K groups inside the launch, 2000 = hipBLASLt.
 

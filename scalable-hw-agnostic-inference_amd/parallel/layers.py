@@ -51,7 +51,8 @@ class _ShardLoadMixin:
 
     # ---- MXFP4 weight-only quantisation (``quantization: mxfp4``): the weight becomes packed e2m1 codes
     # [N, K / 2] + e8m0 group scales (``ops.quantize_mxfp4``), quantised AFTER sharding (a group of 32 never
-    # straddles two ranks); decode GEMMs stream a quarter of the bf16 bytes, larger ones dequantise first.
+    # straddles two ranks); GEMMs of up to ops.MXFP4_FUSED_MAX_ROWS rows stream a quarter of the bf16 bytes, larger
+    # ones dequantise first.
     def quantize_mxfp4_(self) -> None:
         if getattr(self, "weight_scale", None) is not None:
             if not ops.is_mxfp4(self.weight):

@@ -151,8 +151,56 @@ def bench_decode_fp8(rows):
                              bf16_TBps=gb / best["bf16"][0] / 1e3, fp8_eqTBps=gb / best["fp8"][0] / 1e3))
 
 
+def bench_fp4_tile_rows(rows, M, N, K, wts, ncopy, reps):
+    """One M > 64 row of ``bench_fp4``: bf16 ``linear``, MXFP4 through the dequantise route (``MXFP4_PREFILL =
+    "dequant"``: a dequantise pass over the whole matrix, then the bf16 GEMMs) and through the fused tile GEMM
+    (gemm_fp4.hip), same method as the decode rows (rotating weight copies, graph replay, the variants alternating
+    inside every repeat, median and spread)."""
+    a = rnd(M, K)
+    src = {"bf16": "bf16", "dequant": "fp4", "fused": "fp4"}
+    it = {v: 0 for v in src}
+
+    def run(v):
+        it[v] = (it[v] + 1) % ncopy[src[v]]
+        w, sc = wts[src[v]][it[v]]
+        ops.MXFP4_PREFILL = "dequant" if v == "dequant" else "fused"
+        try:
+            return ops.linear(a, w, w_scale=sc)
+        finally:
+            ops.MXFP4_PREFILL = "fused"
+    cap, ops.MXFP4_FUSED_MAX_ROWS = ops.MXFP4_FUSED_MAX_ROWS, 0   # "fused" is the tile GEMM at every M: the row cap
+    try:                                                           # of the route is decided FROM this table
+        return _bench_fp4_tile_rows(rows, M, N, K, ncopy, reps, a, src, run)
+    finally:
+        ops.MXFP4_FUSED_MAX_ROWS = cap
+
+
+def _bench_fp4_tile_rows(rows, M, N, K, ncopy, reps, a, src, run):
+    for v in src:   # tune outside the timing
+        run(v)
+    ts = {v: [] for v in src}
+    for _ in range(reps):
+        for v in src:
+            n = ncopy[src[v]]
+            n_it = n * ((15 + n) // n) if M >= 1024 else n * ((31 + n) // n)
+            ts[v].append(graph_time(lambda: run(v), iters=n_it, reps=2))
+    r = dict(op="prefill_fp4", shape=f"{M}x{N}x{K}")
+    for v in src:
+        t = sorted(ts[v])
+        med = t[len(t) // 2]
+        r[f"{v}_us"] = med * 1e6
+        r[f"{v}_spread_pct"] = 100.0 * (t[-1] - t[0]) / med
+    r["fused_TFLOPs"] = 2.0 * M * N * K / (r["fused_us"] * 1e-6) / 1e12
+    r["fused_vs_dequant"] = r["dequant_us"] / r["fused_us"]
+    r["fused_vs_bf16"] = r["bf16_us"] / r["fused_us"]
+    rows.append(r)
+    print("  ".join(f"{k}={x:.2f}" if isinstance(x, float) else f"{k}={x}" for k, x in r.items()), flush=True)
+
+
 def bench_fp4(rows):
-    """Decode GEMMs of Mistral-7B and a 70B Llama at M = 1 / 16 / 64 with bf16, fp8 (e4m3 + row scales) and MXFP4
+    """MXFP4 GEMMs at more than 64 rows (M = 128 / 256 / 1024 / 4096: ``bench_fp4_tile_rows``; SHAI_FP4_M selects
+    the row counts) and the
+    decode GEMMs of Mistral-7B and a 70B Llama at M = 1 / 16 / 64 with bf16, fp8 (e4m3 + row scales) and MXFP4
     weights: the tuned ``ops.linear`` of each (replayed from a HIP graph), the three variants alternating inside
     every repeat, as the median time, the spread of the repeats ((max - min) / median) and the weight bytes actually streamed over the time.
     Every variant rotates over enough weight copies to exceed the 256 MB Infinity Cache."""
@@ -174,7 +222,10 @@ def bench_fp4(rows):
             if i < ncopy["fp4"]:
                 wts["fp4"].append(ops.quantize_mxfp4(w))
             del w
-        for M in (1, 16, 64):
+        ms = [int(m) for m in os.environ.get("SHAI_FP4_M", "1,16,64,128,256,1024,4096").split(",")]
+        for M in [m for m in ms if m > 64]:
+            bench_fp4_tile_rows(rows, M, N, K, wts, ncopy, reps)
+        for M in [m for m in ms if m <= 64]:
             a = rnd(M, K)
             it = {v: 0 for v in wts}
 
