@@ -208,41 +208,35 @@ bool stream_capturing() {
   return cs != hipStreamCaptureStatusNone;
 }
 
-void launch_skinny2_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool deep) {
+// The split-K workspace of a skinny / fp4 choice: `bytes` of fp32 from the caching allocator (safe under graph
+// capture), alive until `launch` has enqueued its kernels; no workspace (nullptr) for 0 bytes.
+template <class Launch>
+void with_workspace(size_t bytes, const Tensor& like, Launch&& launch) {
   Tensor ws;
   float* wsp = nullptr;
-  const size_t bytes = shai::skinny2_workspace_bytes(g, kg);
   if (bytes > 0) {
     ws = at::empty({(long)(bytes / sizeof(float))}, like.options().dtype(at::kFloat));
     wsp = ws.data_ptr<float>();
   }
-  shai::launch_skinny2(g, wsp, kg, deep, stream());
+  launch(wsp);
+}
+
+void launch_skinny2_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool deep) {
+  with_workspace(shai::skinny2_workspace_bytes(g, kg), like,
+                 [&](float* ws) { shai::launch_skinny2(g, ws, kg, deep, stream()); });
 }
 
 // MXFP4 weights at M <= 64 (csrc/kernels/gemv_fp4.hip): the only kernel of such a problem.  Its choices reuse
 // kSkinnyCfg (split-K with the separate fold) and kSkinnyFixCfg (in-launch fixup) under the problem's own "|mxfp4w" key.
 void launch_skinny_fp4_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
-  Tensor ws;
-  float* wsp = nullptr;
-  const size_t bytes = shai::skinny_fp4_workspace_bytes(g, kg);
-  if (bytes > 0) {
-    ws = at::empty({(long)(bytes / sizeof(float))}, like.options().dtype(at::kFloat));
-    wsp = ws.data_ptr<float>();
-  }
-  shai::launch_skinny_fp4(g, wsp, kg, fixup, stream());
+  with_workspace(shai::skinny_fp4_workspace_bytes(g, kg), like,
+                 [&](float* ws) { shai::launch_skinny_fp4(g, ws, kg, fixup, stream()); });
 }
 
-// MXFP4 weights at M > 64 (csrc/kernels/gemm_fp4.hip): tile config x split count, the workspace allocated as the
-// skinny choices allocate theirs (caching allocator: safe under graph capture)
+// MXFP4 weights at M > 64 (csrc/kernels/gemm_fp4.hip): tile config x split count
 void launch_fp4_tile_choice(const shai::GemmArgs& g, const Tensor& like, int tile, int splits) {
-  Tensor ws;
-  float* wsp = nullptr;
-  const size_t bytes = shai::gemm_fp4_workspace_bytes(g, splits);
-  if (bytes > 0) {
-    ws = at::empty({(long)(bytes / sizeof(float))}, like.options().dtype(at::kFloat));
-    wsp = ws.data_ptr<float>();
-  }
-  shai::launch_gemm_fp4(g, wsp, tile, splits, stream());
+  with_workspace(shai::gemm_fp4_workspace_bytes(g, splits), like,
+                 [&](float* ws) { shai::launch_gemm_fp4(g, ws, tile, splits, stream()); });
 }
 
 Choice fp4_tile_default(const shai::GemmArgs& g) {
@@ -251,14 +245,8 @@ Choice fp4_tile_default(const shai::GemmArgs& g) {
 }
 
 void launch_skinny_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
-  Tensor ws;
-  float* wsp = nullptr;
-  const size_t bytes = shai::skinny_workspace_bytes_kg(g, kg);
-  if (bytes > 0) {
-    ws = at::empty({(long)(bytes / sizeof(float))}, like.options().dtype(at::kFloat));
-    wsp = ws.data_ptr<float>();
-  }
-  shai::launch_skinny_kg(g, wsp, kg, stream(), fixup);
+  with_workspace(shai::skinny_workspace_bytes_kg(g, kg), like,
+                 [&](float* ws) { shai::launch_skinny_kg(g, ws, kg, stream(), fixup); });
 }
 
 // Choice.cfg of the library path: plain GEMMs (no fused epilogue beyond a bias or an unscaled residual) may

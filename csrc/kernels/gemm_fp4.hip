@@ -35,40 +35,14 @@
 //           converts : MFMAs = 1 : 1, 0.59 ds_read per MFMA.  Long prefill.
 // (A 256 x 256 tile would need 2 x 81 KB of LDS; wider N at BM = 128 doubles the converts per CU for the same MFMAs.)
 // Resource table and measurements: profiles/mxfp4_prefill.md.
-#include "common.h"
-#include "launchers.h"
-#include "gemm_epilogue.h"
+// (buffer descriptor, zero-fill sentinel, e8m0_scale and fp4x8_widen: skinny_common.h, shared with gemv_fp4.hip)
+#include "skinny_common.h"
 
 namespace shai {
-
-typedef __bf16 g4_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 g4_bf16x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void g4_lds_void;
 
 constexpr int G4_BK = 128;                 // K per step (4 scale groups)
 constexpr int G4_A_ROW = G4_BK * 2;        // bytes of A per row and step
 constexpr int G4_W_ROW = G4_BK / 2;        // bytes of codes per row and step
-constexpr uint32_t G4_OOB = 0x80000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t g4_rsrc(const void* base, long bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), (short)0, (int)min(bytes, 0x7fffffffL),
-                                           0x00020000);
-}
-
-// 2^(byte - 127) as fp32 (gemv_fp4.hip: bytes stay in [2, 252]; a zero-filled byte reads as 2^-126 beside zero codes)
-__device__ __forceinline__ float g4_scale(uint32_t byte) { return __uint_as_float(max(byte, 1u) << 23); }
-
-// 8 e2m1 codes (one dword, even k in the low nibbles) x scale -> 8 bf16, exact
-__device__ __forceinline__ g4_bf16x8 g4_widen(uint32_t codes, float scale) {
-  g4_bf16x8 r;
-  const g4_bf16x2 a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 0);
-  const g4_bf16x2 b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 1);
-  const g4_bf16x2 c = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 2);
-  const g4_bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 3);
-  r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1];
-  r[4] = c[0]; r[5] = c[1]; r[6] = d[0]; r[7] = d[1];
-  return r;
-}
 
 template <int BM, int BN, int WM, int WN, int STAGES>
 struct G4Geom {
@@ -121,9 +95,9 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_fp4_kernel(const GemmArgs p
   const int nk = SPLITK ? max(0, min(ksteps, t0 + kg_steps) - t0) : ksteps;
 
   const long a_bytes = (long)p.M * p.lda * 2, w_bytes = (long)p.N * p.ldw, s_bytes = (long)ksteps * p.N * 4;
-  const __amdgpu_buffer_rsrc_t rA = g4_rsrc(p.A, a_bytes);
-  const __amdgpu_buffer_rsrc_t rW = g4_rsrc(p.W, w_bytes);  // ldw: bytes
-  const __amdgpu_buffer_rsrc_t rS = g4_rsrc(p.w_mx_scale, s_bytes);
+  const __amdgpu_buffer_rsrc_t rA = buf_rsrc(p.A, a_bytes);
+  const __amdgpu_buffer_rsrc_t rW = buf_rsrc(p.W, w_bytes);  // ldw: bytes
+  const __amdgpu_buffer_rsrc_t rS = buf_rsrc(p.w_mx_scale, s_bytes);
 
   // DMA geometry: LDS images are lane-linear per wave instruction, the swizzle is on the source address
   uint32_t a_off[JA], w_off[JW];
@@ -131,16 +105,16 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_fp4_kernel(const GemmArgs p
   for (int j = 0; j < JA; ++j) {  // instruction wid JA + j: tile rows 4 (wid JA + j) + (lane >> 4), position lane & 15
     const int r = 4 * (wid * JA + j) + (lane >> 4), m = m0 + r;
     const int c = (lane & 15) ^ (r & 15);
-    a_off[j] = m < p.M ? (uint32_t)(((long)m * p.lda + c * 8) * 2) : G4_OOB;
+    a_off[j] = m < p.M ? (uint32_t)(((long)m * p.lda + c * 8) * 2) : kDmaOob;
   }
 #pragma unroll
   for (int j = 0; j < JW; ++j) {  // instruction wid JW + j: tile rows 16 (wid JW + j) + (lane >> 2), position lane & 3
     const int r = 16 * (wid * JW + j) + (lane >> 2), n = n0 + r;
     const int c = (lane & 3) ^ ((r >> 2) & 3);
-    w_off[j] = n < p.N ? (uint32_t)((long)n * p.ldw + c * 16) : G4_OOB;
+    w_off[j] = n < p.N ? (uint32_t)((long)n * p.ldw + c * 16) : kDmaOob;
   }
   // scales: lanes 0-31 fetch the dword of tile row 32 wid + lane
-  const uint32_t s_off = (lane < 32 && n0 + 32 * wid + lane < p.N) ? (uint32_t)((n0 + 32 * wid + lane) * 4) : G4_OOB;
+  const uint32_t s_off = (lane < 32 && n0 + 32 * wid + lane < p.N) ? (uint32_t)((n0 + 32 * wid + lane) * 4) : kDmaOob;
 
   auto stage = [&](int buf, int step) {
     SHAI_DASSERT(buf >= 0 && buf < STAGES);
@@ -151,21 +125,21 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_fp4_kernel(const GemmArgs p
 #pragma unroll
     for (int j = 0; j < JW; ++j) {  // K tail: whole 32-code chunks past K read as zeros
       const int c = (lane & 3) ^ (((16 * (wid * JW + j) + (lane >> 2)) >> 2) & 3);
-      const uint32_t off = (w_off[j] != G4_OOB && k0 + c * 32 < (uint32_t)p.K) ? w_off[j] + (k0 >> 1) : G4_OOB;
-      SHAI_DASSERT_DMA(off, w_bytes, G4_OOB);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (g4_lds_void*)(sw + (wid * JW + j) * 1024), 16, off, 0, 0, 0);
+      const uint32_t off = (w_off[j] != kDmaOob && k0 + c * 32 < (uint32_t)p.K) ? w_off[j] + (k0 >> 1) : kDmaOob;
+      SHAI_DASSERT_DMA(off, w_bytes, kDmaOob);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rW, (lds_void*)(sw + (wid * JW + j) * 1024), 16, off, 0, 0, 0);
     }
     {
-      const uint32_t off = s_off != G4_OOB ? s_off + (uint32_t)(t0 + step) * (uint32_t)p.N * 4u : G4_OOB;
-      SHAI_DASSERT(off >= G4_OOB || (long)off + 4 <= s_bytes);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rS, (g4_lds_void*)(ss + wid * 256), 4, off, 0, 0, 0);
+      const uint32_t off = s_off != kDmaOob ? s_off + (uint32_t)(t0 + step) * (uint32_t)p.N * 4u : kDmaOob;
+      SHAI_DASSERT(off >= kDmaOob || (long)off + 4 <= s_bytes);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rS, (lds_void*)(ss + wid * 256), 4, off, 0, 0, 0);
     }
 #pragma unroll
     for (int j = 0; j < JA; ++j) {
       const int c = (lane & 15) ^ ((4 * j + (lane >> 4)) & 15);  // (4 wid JA) % 16 == 0
-      const uint32_t off = (a_off[j] != G4_OOB && k0 + c * 8 < (uint32_t)p.K) ? a_off[j] + k0 * 2 : G4_OOB;
-      SHAI_DASSERT_DMA(off, a_bytes, G4_OOB);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (g4_lds_void*)(sa + (wid * JA + j) * 1024), 16, off, 0, 0, 0);
+      const uint32_t off = (a_off[j] != kDmaOob && k0 + c * 8 < (uint32_t)p.K) ? a_off[j] + k0 * 2 : kDmaOob;
+      SHAI_DASSERT_DMA(off, a_bytes, kDmaOob);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rA, (lds_void*)(sa + (wid * JA + j) * 1024), 16, off, 0, 0, 0);
     }
   };
 
@@ -194,29 +168,29 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_fp4_kernel(const GemmArgs p
         const int c = 2 * fh + i;  // 16-B code chunk = scale group of the step
         SHAI_DASSERT(wrow * G4_W_ROW + ((c ^ wswz) << 4) + 16 <= G::W_BYTES);
         cw[jn][i] = *reinterpret_cast<const uint4_*>(sw + wrow * G4_W_ROW + ((c ^ wswz) << 4));
-        sc[jn][i] = g4_scale((sc4 >> (8 * c)) & 0xffu);
+        sc[jn][i] = e8m0_scale((sc4 >> (8 * c)) & 0xffu);
       }
     }
     // 8 groups of IM x JN MFMAs: group g = 4 i + j takes dword j of code chunk c = 2 fh + i (k = 32 c + 8 j .. + 7)
     // against A chunk 4 c + j.  The A fragments of group g + 1 are read before group g's MFMAs issue, so one wave per
     // SIMD does not sit out the LDS latency between groups.
-    auto load_x = [&](int g, g4_bf16x8* xf) {
+    auto load_x = [&](int g, bf16x8* xf) {
       const int xc = 4 * (2 * fh + (g >> 2)) + (g & 3);
 #pragma unroll
       for (int im = 0; im < IM; ++im) {
         const int xrow = wm * TM + im * 32 + fr;
         SHAI_DASSERT(xrow * G4_A_ROW + ((xc ^ (xrow & 15)) << 4) + 16 <= G::A_BYTES);
-        xf[im] = *reinterpret_cast<const g4_bf16x8*>(sa + xrow * G4_A_ROW + ((xc ^ (xrow & 15)) << 4));
+        xf[im] = *reinterpret_cast<const bf16x8*>(sa + xrow * G4_A_ROW + ((xc ^ (xrow & 15)) << 4));
       }
     };
-    g4_bf16x8 xf[2][IM];
+    bf16x8 xf[2][IM];
     load_x(0, xf[0]);
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       if (g + 1 < 8) load_x(g + 1, xf[(g + 1) & 1]);
 #pragma unroll
       for (int jn = 0; jn < JN; ++jn) {
-        const g4_bf16x8 wf = g4_widen(cw[jn][g >> 2][g & 3], sc[jn][g >> 2]);
+        const bf16x8 wf = fp4x8_widen(cw[jn][g >> 2][g & 3], sc[jn][g >> 2]);
 #pragma unroll
         for (int im = 0; im < IM; ++im)
           acc[im][jn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf, xf[g & 1][im], acc[im][jn], 0, 0, 0);
@@ -316,12 +290,7 @@ int gemm_fp4_splits(const GemmArgs& a, int tile) {
   return s;
 }
 
-int gemm_fp4_max_splits(const GemmArgs& a) {
-  const int ksteps = (a.K + G4_BK - 1) / G4_BK;
-  int s = 1;
-  while (s < 16 && ksteps / (s * 2) >= 2) s *= 2;
-  return s;
-}
+int gemm_fp4_max_splits(const GemmArgs& a) { return max_kgroups((a.K + G4_BK - 1) / G4_BK); }
 
 size_t gemm_fp4_workspace_bytes(const GemmArgs& a, int splits) {
   return splits > 1 ? (size_t)splits * a.M * a.N * sizeof(float) : 0;  // [split][M][N]
@@ -336,35 +305,20 @@ static void launch_g4_tile(const GemmArgs& a, float* ws, int splits, int kg_step
     gemm_fp4_kernel<BM, BN, WM, WN, STAGES, false, ACT_NONE, true><<<dim3(tiles, splits), block, lds, s>>>(a, ws, kg_steps);
     return;
   }
-#define G4(G, A) gemm_fp4_kernel<BM, BN, WM, WN, STAGES, G, A, false><<<dim3(tiles), block, lds, s>>>(a, nullptr, 0)
-  if (a.glu) {  // tile_act_supported: SILU / GELU / GELU_TANH
-    if (a.act == ACT_SILU) G4(true, ACT_SILU);
-    else if (a.act == ACT_GELU_TANH) G4(true, ACT_GELU_TANH);
-    else G4(true, ACT_GELU);
-    return;
-  }
-  switch (a.act) {
-    case ACT_SILU: G4(false, ACT_SILU); break;
-    case ACT_GELU: G4(false, ACT_GELU); break;
-    case ACT_GELU_TANH: G4(false, ACT_GELU_TANH); break;
-    case ACT_QUICK_GELU: G4(false, ACT_QUICK_GELU); break;
-    case ACT_RELU: G4(false, ACT_RELU); break;
-    default: G4(false, ACT_NONE); break;
-  }
-#undef G4
+  // GLU: tile_act_supported admits SILU / GELU / GELU_TANH only; no folded-RMSNorm forms
+  constexpr unsigned kGluActs = act_bit(ACT_SILU) | act_bit(ACT_GELU) | act_bit(ACT_GELU_TANH);
+  dispatch_epilogue<kActsAll, kGluActs, ACT_GELU, false>(a, [&](auto glu, auto act, auto) {
+    gemm_fp4_kernel<BM, BN, WM, WN, STAGES, glu(), act(), false><<<dim3(tiles), block, lds, s>>>(a, nullptr, 0);
+  });
 }
 
 // tile: 0 = 128 x 128, 1 = 256 x 128; splits K groups (needs ws of gemm_fp4_workspace_bytes, else unsplit), folded by
 // launch_splitk_epilogue in split order
 void launch_gemm_fp4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s) {
-  const int ksteps = (a.K + G4_BK - 1) / G4_BK;
-  if (ws == nullptr || splits < 1) splits = 1;
-  if (splits > ksteps) splits = ksteps;
-  const int kg_steps = (ksteps + splits - 1) / splits;
-  splits = (ksteps + kg_steps - 1) / kg_steps;  // no empty K groups
-  if (tile == 1) launch_g4_tile<256, 128, 2, 2, 2>(a, ws, splits, kg_steps, s);
-  else launch_g4_tile<128, 128, 2, 2, 3>(a, ws, splits, kg_steps, s);
-  if (splits > 1) launch_splitk_epilogue(a, ws, splits, s);
+  const KSplit ks = split_ksteps((a.K + G4_BK - 1) / G4_BK, ws != nullptr ? splits : 1);
+  if (tile == 1) launch_g4_tile<256, 128, 2, 2, 2>(a, ws, ks.kg, ks.kg_steps, s);
+  else launch_g4_tile<128, 128, 2, 2, 3>(a, ws, ks.kg, ks.kg_steps, s);
+  if (ks.kg > 1) launch_splitk_epilogue(a, ws, ks.kg, s);
 }
 
 }  // namespace shai

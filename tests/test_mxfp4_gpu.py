@@ -169,3 +169,17 @@ def test_mxfp4_llm_engine(cuda):
             margin = (rowl[want[t]] - rowl[o[t]]).item()
             assert margin <= 2 * 3e-2 * rowl.abs().max().item(), (b, t, o, want, margin)
             break
+
+
+def test_fp4_skinny_fixup_deterministic_graph_and_streams(cuda):
+    """The in-launch fixup of the fp4 skinny kernel (forced 1104): M = 33, N = 320 (2.5 tiles), K = 2112 (16.5 steps:
+    K groups of 5, 5, 5 and 2), GLU + folded RMSNorm -- eager runs, graph replays and two streams at once are
+    bitwise equal."""
+    from test_skinny_gpu import check_fixup_repeatable
+    torch.manual_seed(11)
+    M, N, K = 33, 320, 2112
+    wq, s, _ = _quantised(N, K, 11, cuda)
+    x = (torch.randn(M, K, device=cuda) * 2).bfloat16()
+    check_fixup_repeatable(
+        lambda out: ops.gemm_into(x, wq, out, act="silu", glu=True, rms_eps=1e-5, w_scale=s, force_cfg=1104),
+        (M, N // 2), cuda)

@@ -423,3 +423,56 @@ def test_skinny2_glu_residual_and_graph(cuda, cfg):
         g.replay()
         torch.cuda.synchronize()
         assert _rel(o2, x.float() @ w.float().t()) < 1e-2
+
+
+def check_fixup_repeatable(run, out_shape, cuda):
+    """What the in-launch split-K fixup must keep, for a launch ``run(out)``: two eager runs and two replays of one
+    captured graph are bitwise equal (slabs summed in K-group order, tickets re-armed), and the same call on two
+    streams at once (each stream its own ticket slice) gives the single-stream result.  The eager runs come first:
+    they create the ticket pool, without which a launch under capture could not take a slice (and the bf16 wide
+    kernel would run unsplit)."""
+    def new():
+        return torch.full(out_shape, 3.0, device=cuda, dtype=torch.bfloat16)
+    want = new()
+    run(want)
+    again = new()
+    run(again)
+    gout = new()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        run(gout)                                   # warm-up on a side stream, as torch asks before a capture
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        run(gout)
+    replays = []
+    for _ in range(2):
+        gout.fill_(3.0)
+        g.replay()
+        torch.cuda.synchronize()
+        replays.append(gout.clone())
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    outs = [[new() for _ in range(4)] for _ in streams]
+    for s in streams:
+        s.wait_stream(torch.cuda.current_stream())
+    for rep in range(4):
+        for s, o in zip(streams, outs):
+            with torch.cuda.stream(s):
+                run(o[rep])
+    torch.cuda.synchronize()
+    assert torch.isfinite(want.float()).all() and not (want == 3.0).all()
+    for i, o in enumerate([again] + replays + outs[0] + outs[1]):
+        assert torch.equal(o, want), i
+
+
+@pytest.mark.parametrize("cfg", [SKINNY2 + 4, SKINNY2_DEEP + 4])
+def test_skinny2_fixup_deterministic_graph_and_streams(cuda, cfg):
+    """The wide kernel's fixup (skinny_rows_kernel with bf16 weights, both ring depths): M = 33 (two X groups, one
+    ragged), N = 320 (2.5 tiles), K = 2112 (33 steps: K groups of 9, 9, 9 and 6), GLU + folded RMSNorm."""
+    torch.manual_seed(11)
+    M, N, K = 33, 320, 2112
+    x = (torch.randn(M, K, device=cuda) * 2).bfloat16()
+    w = (torch.randn(N, K, device=cuda) / K ** 0.5).bfloat16()
+    check_fixup_repeatable(
+        lambda out: ops.gemm_into(x, w, out, act="silu", glu=True, rms_eps=1e-5, force_cfg=cfg), (M, N // 2), cuda)
