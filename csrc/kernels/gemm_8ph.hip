@@ -28,7 +28,15 @@
 //   (row >> 1) & 7) applied to the per-lane SOURCE address and to the ds_read address: every 16-lane
 //   ds_read_b128 group touches 16 distinct 16-B bank slots (conflict-free).
 // * Implicit-GEMM conv when Cin (and the concat split Cin1) are multiples of 64: each K-tile then lies
-//   inside one filter tap and one source tensor, so only (ih, iw) of the lane's 4 rows change per tile.
+//   inside one filter tap and one source tensor.  Inside one (tap, source) segment of Cin / 64 consecutive
+//   K-tiles a lane's 4 source addresses advance by 128 bytes per tile and their validity does not change,
+//   so the staging state is one running byte offset per A piece plus the segment's descriptor: a piece is
+//   an m0 write and one `buffer_load ... lds`, with no address arithmetic, compare or exec masking in the
+//   phases that issue DMA.  The state moves to the next K-tile in the phase-3 load segment (no DMA, 4
+//   reads): 4 adds, or, behind a wave-uniform branch taken when the position enters a new tap or the
+//   second source of a concat, the im2col address from scratch (g4_conv_off).  Split-K (starts mid-tap)
+//   and every output tile of the persistent loop seed the state from their first K position.  The conv's
+//   K and split-K bounds are whole K-tiles, so its W pieces carry no ragged-K test either.
 // * Range-checked buffer descriptors give the zero fill (M/N/K tails, conv padding); XCD-aware
 //   bijective block remap + grouped M ordering.
 // * Persistent form (VAR bit 3, configs kV4Cfg + 2 / + 3): one workgroup per CU walks output tiles
@@ -110,6 +118,28 @@ struct G4ConvPos {
   int kh, kw, c;
 };
 
+// Byte offset of one lane's 16-B source chunk of a conv A row for filter tap (kh, kw): ihw the row's top-left tap
+// position packed ih0 * 65536 + (iw0 & 0xffff) (one register held across the K loop; both are 16-bit signed:
+// G4_POSMAX), pix its pixel index (CONV 2: n * H), kc the chunk's byte offset inside the K-tile, cs / cb the source
+// tensor's channel stride and the K-tile's channel base in it.  G4_OOB (zero fill) when the tap falls on padding or
+// the row is beyond M (ih0 = G4_NOROW).
+constexpr int G4_POSMAX = 1 << 14;  // bound on pad and on the strided / upsampled input extent (gemm4_supported)
+constexpr int G4_NOROW = -G4_POSMAX;
+template <int CONV>
+__device__ __forceinline__ uint32_t g4_conv_off(const GemmArgs& p, int ihw, int pix, uint32_t kc, int kh, int kw, int cs,
+                                                int cb) {
+  const int ih = (ihw >> 16) + kh, iw = (int)(short)ihw + kw;
+  if constexpr (CONV == 1 || CONV == 3) {
+    const bool ok = ((unsigned)ih < (unsigned)p.H) & ((unsigned)iw < (unsigned)p.Wd);
+    const int tapd = kh * p.Wd + kw;
+    return ok ? (uint32_t)((pix + tapd) * cs + cb) * 2 + kc : G4_OOB;
+  } else {
+    const bool ok = ((unsigned)ih < (unsigned)(2 * p.H)) & ((unsigned)iw < (unsigned)(2 * p.Wd));
+    const int px = (pix + (ih >> 1)) * p.Wd + (iw >> 1);
+    return ok ? (uint32_t)(px * cs + cb) * 2 + kc : G4_OOB;
+  }
+}
+
 // CONV: 0 plain GEMM, 1 implicit-GEMM conv, 2 implicit-GEMM conv over a nearest-2x upsampled input,
 // 3 the same upsample + 3x3 conv decomposed by output phase (GemmArgs::upsample == 2): an output pixel
 // (2i + py, 2j + px) of the upsampled grid reads only 2 x 2 distinct source pixels (rows i - 1 + py + a, columns
@@ -171,12 +201,15 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
   // ---- staging geometry: DMA wave-instruction j fills 8 LDS rows x 128 B (lane-linear); the lane's
   // source chunk is the swizzled one.  Per-row byte offsets are precomputed; an invalid row's offset
   // carries the OOB bit, which survives the per-tile additions (< 2^31) and reads as zero fill.
+  if constexpr (CONV != 0) SHAI_DASSERT(p.K % G4_BK == 0 && k_per_split % G4_BK == 0);  // whole K-tiles: no ragged-K test
   const int lrow0 = lane >> 3, lpos0 = lane & 7;
   int kch[4];            // k offset of the lane's source chunk within the K-tile (A rows)
   int kchw[NWJ];         // same for the W rows
   uint32_t woff[NWJ];    // W row byte offset + chunk
-  uint32_t aoff[4];      // plain GEMM: A row byte offset + chunk
-  int ih0[4], iw0[4];    // conv: top-left input tap position of the output pixel (upsampled grid for CONV 2)
+  uint32_t aoff[4];      // plain GEMM: A row byte offset + chunk; conv: CURRENT source byte offset (see conv_seed)
+  uint32_t kc2 = 0;      // conv: 2 kch[0]; rows j and j + 2 share a chunk, odd j have it ^ 64 (the swizzle's row bit 3)
+  int ihw[4];            // conv: top-left input tap position (ih0, iw0) of the output pixel (upsampled grid for
+                         // CONV 2), packed ih0 * 65536 + (iw0 & 0xffff) (g4_conv_off; host: gemm4_supported)
   int pix[4];            // conv (CONV 1): pixel index of (ih0, iw0); CONV 2: n * H
   // per-tile row offsets for the tile at (m0, n0); cheap enough to recompute rather than hold live
   // across the persistent loop's epilogue
@@ -208,39 +241,66 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
         const int cn = mm / hw;
         const int rem = mm - cn * hw;
         const int coh = rem / p.OW, cow = rem - coh * p.OW;
+        int ih0, iw0;
         if constexpr (CONV == 3) {
           // row (image, phase, i, j): 2 x 2 taps from source row i - 1 + py, column j - 1 + px
           const Up2Row q = up2_row(p, mm);
-          ih0[j] = m < p.M ? q.si - 1 + (q.ph >> 1) : -(1 << 24);
-          iw0[j] = q.sj - 1 + (q.ph & 1);
-          pix[j] = (q.img * p.H + ih0[j]) * p.Wd + iw0[j];
+          ih0 = m < p.M ? q.si - 1 + (q.ph >> 1) : G4_NOROW;
+          iw0 = q.sj - 1 + (q.ph & 1);
+          pix[j] = (q.img * p.H + ih0) * p.Wd + iw0;
           (void)cn;
           (void)coh;
           (void)cow;
         } else if constexpr (CONV == 1) {
-          ih0[j] = m < p.M ? coh * p.stride - p.pad : -(1 << 24);
-          iw0[j] = cow * p.stride - p.pad;
-          pix[j] = (cn * p.H + ih0[j]) * p.Wd + iw0[j];
+          ih0 = m < p.M ? coh * p.stride - p.pad : G4_NOROW;
+          iw0 = cow * p.stride - p.pad;
+          pix[j] = (cn * p.H + ih0) * p.Wd + iw0;
         } else {
-          ih0[j] = m < p.M ? coh - p.pad : -(1 << 24);
-          iw0[j] = cow - p.pad;
+          ih0 = m < p.M ? coh - p.pad : G4_NOROW;
+          iw0 = cow - p.pad;
           pix[j] = cn * p.H;
         }
-        aoff[j] = (uint32_t)kch[j] * 2;
+        ihw[j] = ih0 * 65536 + (iw0 & 0xffff);
       }
     }
+    if constexpr (CONV != 0) kc2 = (uint32_t)kch[0] * 2;
   };
   setup();
   const int cs_a = p.A2 ? p.Cin1 : p.Cin;  // channel stride (elements per pixel) of source A / A2
   const int cs_b = p.Cin - p.Cin1;
 
-  // Issue DMA g of the K-tile at k0 (conv position cp) into buffer buf: g < 8: even = A rows j = g / 2,
-  // odd = W rows j = g / 2 (A and W interleave so every phase that stages issues both kinds); g = 8: W
-  // rows 4 (BN = 320).
-  auto stage_one = [&](int buf, int k0, const G4ConvPos& cp, int g) {
+  // ---- conv staging state.  Inside one (filter tap, source tensor) segment of consecutive K-tiles a lane's four
+  // source addresses advance by exactly 128 bytes per tile and their validity does not change, so the state is the
+  // CURRENT byte offset per A piece (aoff[], G4_OOB-tagged when the tap falls on padding or the row is beyond M)
+  // and the segment's descriptor (rcur), both for the K-tile at cpos: a piece is one register and one instruction.
+  // The im2col address is computed only when the position enters a new segment (conv_seed).
+  G4ConvPos cpos{0, 0, 0};
+  __amdgpu_buffer_rsrc_t rcur = rA;
+  // full state for the K-tile at (kh, kw, c) (any position: split-K starts mid-tap)
+  auto conv_seed = [&](int kh, int kw, int c) {
+    if constexpr (CONV != 0) {
+      cpos = G4ConvPos{kh, kw, c};
+      const bool second = p.A2 != nullptr && c >= p.Cin1;
+      rcur = second ? rA2 : rA;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // opaque: what is derived from the packed position is rebuilt here, in the rare path, not hoisted out of
+        // the K loop and held live beside the accumulators
+        asm volatile("" : "+v"(ihw[j]));
+        aoff[j] = g4_conv_off<CONV>(p, ihw[j], pix[j], kc2 ^ ((uint32_t)(j & 1) << 6), kh, kw, second ? cs_b : cs_a,
+                                    second ? c - p.Cin1 : c);
+      }
+    }
+  };
+
+  // Issue DMA g of the K-tile at k0 (conv: the tile the staging state stands at) into buffer buf: g < 8: even =
+  // A rows j = g / 2, odd = W rows j = g / 2 (A and W interleave so every phase that stages issues both kinds);
+  // g = 8: W rows 4 (BN = 320).
+  auto stage_one = [&](int buf, int k0, int g) {
     bf16_t* sa = g4_smem + buf * G4_STAGE;
     const int j = g >> 1;
-    const bool ktail = k0 + G4_BK > k_end;  // uniform: only the last K-tile of a ragged K checks chunks
+    // uniform: only the last K-tile of a ragged K checks chunks; the conv's K and split-K bounds are whole tiles
+    const bool ktail = CONV == 0 && k0 + G4_BK > k_end;
     if ((g & 1) || g == 8) {
       uint32_t off = woff[j] + (uint32_t)k0 * 2;
       if (ktail && k0 + kchw[j] >= k_end) off = G4_OOB;
@@ -255,34 +315,24 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
       SHAI_DASSERT_DMA(off, (long)p.M * p.lda * 2, G4_OOB);
       g4_glds(rA, sa + (wid * 32 + j * 8) * G4_BK, off);
     } else {
-      const bool second = p.A2 != nullptr && cp.c >= p.Cin1;
-      const int cs = second ? cs_b : cs_a;
-      const int cb = second ? cp.c - p.Cin1 : cp.c;
-      const int ih = ih0[j] + cp.kh, iw = iw0[j] + cp.kw;
-      uint32_t off;
-      if constexpr (CONV == 1 || CONV == 3) {
-        const bool ok = ((unsigned)ih < (unsigned)p.H) & ((unsigned)iw < (unsigned)p.Wd);
-        const int tapd = cp.kh * p.Wd + cp.kw;
-        off = ok ? (uint32_t)((pix[j] + tapd) * cs + cb) * 2 + aoff[j] : G4_OOB;
-      } else {
-        const bool ok = ((unsigned)ih < (unsigned)(2 * p.H)) & ((unsigned)iw < (unsigned)(2 * p.Wd));
-        const int px = (pix[j] + (ih >> 1)) * p.Wd + (iw >> 1);
-        off = ok ? (uint32_t)(px * cs + cb) * 2 + aoff[j] : G4_OOB;
-      }
-      if (k0 >= k_end) off = G4_OOB;
-      SHAI_DASSERT_DMA(off, (long)p.Nimg * p.H * p.Wd * cs * 2, G4_OOB);
-      g4_glds(second ? rA2 : rA, sa + (wid * 32 + j * 8) * G4_BK, off);
+      // the running offset is the from-scratch im2col offset of this K-tile (or both carry the OOB bit)
+      SHAI_DASSERT(k0 < k_end && k0 == ((cpos.kh * p.KW + cpos.kw) * p.Cin + cpos.c));
+      [[maybe_unused]] const bool second = p.A2 != nullptr && cpos.c >= p.Cin1;
+      [[maybe_unused]] const uint32_t want =
+          g4_conv_off<CONV>(p, ihw[j], pix[j], kc2 ^ ((uint32_t)(j & 1) << 6), cpos.kh, cpos.kw,
+                            second ? cs_b : cs_a, second ? cpos.c - p.Cin1 : cpos.c);
+      SHAI_DASSERT(aoff[j] == want || (aoff[j] >= G4_OOB && want >= G4_OOB));
+      SHAI_DASSERT_DMA(aoff[j], (long)p.Nimg * p.H * p.Wd * (second ? cs_b : cs_a) * 2, G4_OOB);
+      g4_glds(rcur, sa + (wid * 32 + j * 8) * G4_BK, aoff[j]);
     }
   };
-  auto conv_pos = [&](int k0) {
-    G4ConvPos cp{0, 0, 0};
+  // staging state -> the K-tile at k0
+  auto conv_seek = [&](int k0) {
     if constexpr (CONV != 0) {
       const int tap = k0 / p.Cin;
-      cp.c = k0 - tap * p.Cin;
-      cp.kh = tap / p.KW;
-      cp.kw = tap - cp.kh * p.KW;
+      const int kh = tap / p.KW;
+      conv_seed(kh, tap - kh * p.KW, k0 - tap * p.Cin);
     }
-    return cp;
   };
   auto conv_advance = [&](G4ConvPos& cp) {
     if constexpr (CONV != 0) {
@@ -296,16 +346,30 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
       }
     }
   };
+  // staging state -> the next K-tile: a wave-uniform branch, taken every Cin / 64 tiles (Cin1 / 64 and (Cin - Cin1) / 64
+  // with a concat), recomputes the addresses at a tap or source boundary; every other tile is one add per piece
+  auto conv_step = [&]() {
+    if constexpr (CONV != 0) {
+      conv_advance(cpos);
+      if (cpos.c == 0 || (p.A2 != nullptr && cpos.c == p.Cin1)) {
+        conv_seed(cpos.kh, cpos.kw, cpos.c);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) aoff[j] += 2 * G4_BK;
+      }
+    }
+  };
 
   const int fr = lane & 15, fq = lane >> 4;
   const int nk = k_end > k_begin ? (k_end - k_begin + G4_BK - 1) / G4_BK : 0;
 
-  // prologue: K-tile 0 of the first output tile -> buffer 0
-  G4ConvPos cpos = conv_pos(k_begin);
+  // prologue: K-tile 0 of the first output tile -> buffer 0; the staging state then stands at K-tile 1
+  conv_seek(k_begin);
   if (nk > 0) {
 #pragma unroll
-    for (int g = 0; g < GT; ++g) stage_one(0, k_begin, cpos, g);
+    for (int g = 0; g < GT; ++g) stage_one(0, k_begin, g);
   }
+  conv_seek(k_begin + G4_BK);
   bf16x8q wf[NJ], xf[4];
   // VAR bit 5 (persistent only): the wide epilogue's stores stay in flight into the next tile.  The top of
   // the loop then waits only for the next tile's first K-tile (DMA issued BEFORE the epilogue): vmcnt
@@ -339,8 +403,7 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
     for (int t = 0; t < nk; ++t) {
       const int cur = t & 1;
       const bool pre = t + 1 < nk;
-      const int knext = k_begin + (t + 1) * G4_BK;
-      conv_advance(cpos);  // position of tile t + 1
+      const int knext = k_begin + (t + 1) * G4_BK;  // (conv: the tile the staging state stands at)
       const bf16_t* sa = g4_smem + cur * G4_STAGE;
       const bf16_t* sw = sa + G4_BM * G4_BK;
 #pragma unroll
@@ -351,7 +414,7 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
         const int g_hi = ph == 0 ? G4_G1 : ph == 1 ? G4_G2 : ph == 2 ? G4_G3 : GT;
         if (pre) {
 #pragma unroll
-          for (int g = g_lo; g < g_hi; ++g) stage_one(cur ^ 1, knext, cpos, g);
+          for (int g = g_lo; g < g_hi; ++g) stage_one(cur ^ 1, knext, g);
         }
         if (mh == 0) {
 #pragma unroll
@@ -361,6 +424,9 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
 #pragma unroll
         for (int i = 0; i < 4; ++i)
           xf[i] = *reinterpret_cast<const bf16x8q*>(sa + g4_swz(wm * 128 + (mh * 4 + i) * 16 + frl, ks * 4 + fql));
+        // every piece of tile t + 1 is issued by now (G4_G3 == GT): the staging state moves on to tile t + 2 here,
+        // in the one load segment that issues no DMA and the fewest reads, under the latency of those reads
+        if (ph == 3) conv_step();
         if (ph == 3) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's DMA of tile t+1 landed
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
@@ -392,9 +458,9 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
         vb += gridDim.x;
         tile_origin(vb, m0, n0);
         setup();
-        cpos = conv_pos(k_begin);
+        conv_seek(k_begin);
 #pragma unroll
-        for (int g = 0; g < GT; ++g) stage_one(0, k_begin, cpos, g);
+        for (int g = 0; g < GT; ++g) stage_one(0, k_begin, g);
         if constexpr (NODRAIN) {  // pin the DMA ahead of the epilogue's loads and stores (vmcnt order)
           asm volatile("" ::: "memory");
           __builtin_amdgcn_sched_barrier(0);
@@ -789,6 +855,7 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
     epilogue(em0, en0);
     if (!more) break;
     setup();  // the next tile's offsets again (dead across the epilogue, so they cost no registers there)
+    conv_seek(k_begin + G4_BK);  // its K-tile 0 is in flight: the staging state stands at K-tile 1
   }
 }
 
@@ -801,6 +868,9 @@ bool gemm4_supported(const GemmArgs& a) {
     return false;
   if (a.conv) {
     if (a.Cin % 64 != 0) return false;
+    // tap positions are held packed in 16 bits each (g4_conv_off)
+    if (a.pad >= G4_POSMAX || (long)a.OH * a.stride >= G4_POSMAX || (long)a.OW * a.stride >= G4_POSMAX) return false;
+    if (a.KH >= G4_POSMAX || a.KW >= G4_POSMAX) return false;
     if (a.A2 != nullptr && a.Cin1 % 64 != 0) return false;
     if (a.upsample == 2) {  // phase conv: one image and phase per tile, output rows remapped (no residual / row stats)
       if (a.KH != 2 || a.KW != 2 || a.OH != 2 * a.H || a.OW != 2 * a.Wd) return false;
