@@ -1288,13 +1288,24 @@ void conv2d(const Tensor& x, const optional<Tensor>& x2, const Tensor& w, const 
 // ---------------------------------------------------------------- attention
 void flash_attn(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, double scale, bool causal,
                 int64_t causal_offset, const optional<Tensor>& kv_lens, const optional<Tensor>& q_lens,
-                const optional<Tensor>& bias, const optional<Tensor>& block_table) {
+                const optional<Tensor>& bias, const optional<Tensor>& block_table, double k_scale,
+                double v_scale) {
   check_rows(q, "q");
-  check_rows(k, "k");
-  check_rows(v, "v");
+  // fp8 (e4m3fn) k / v: the paged KV cache read directly (kv8_cache's layout checks stand in for check_rows)
+  const bool f8 = kv8_cache(k, v, k_scale, v_scale);
+  if (f8) {
+    SHAI_CHECK(block_table.has_value(), "flash_attn: fp8 k / v are a paged KV cache and need a block_table");
+    SHAI_CHECK(!bias.has_value(), "flash_attn: no bias with an fp8 KV cache");
+  } else {
+    check_rows(k, "k");
+    check_rows(v, "v");
+  }
   check_rows(o, "o");
   SHAI_CHECK(q.dim() == 4 && o.dim() == 4, "q/o must be [B, S, H, D]");
   shai::AttnArgs a{};
+  a.kv_fp8 = f8;
+  a.k_scale = (float)k_scale;
+  a.v_scale = (float)v_scale;
   a.B = q.size(0);
   a.Sq = q.size(1);
   a.Hq = q.size(2);
@@ -1363,12 +1374,15 @@ void flash_attn(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor&
 // of its block table; causal with offset kv_len - q_len.  max_q = max(q_lens) sizes the grid.
 void paged_attn_varlen(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& o,
                        const Tensor& block_table, const Tensor& kv_lens, const Tensor& q_lens, const Tensor& q_start,
-                       int64_t max_q, double scale, bool causal) {
+                       int64_t max_q, double scale, bool causal, double k_scale, double v_scale) {
   check_rows(q, "q");
   check_rows(o, "o");
   SHAI_CHECK(q.dim() == 3 && o.dim() == 3 && q.sizes() == o.sizes(), "q/o must be [T, H, D]");
-  check_bf16(k_cache, "k_cache");
-  check_bf16(v_cache, "v_cache");
+  const bool f8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
+  if (!f8) {
+    check_bf16(k_cache, "k_cache");
+    check_bf16(v_cache, "v_cache");
+  }
   check_i32(block_table, "block_table");
   check_i32(kv_lens, "kv_lens");
   check_i32(q_lens, "q_lens");
@@ -1403,6 +1417,9 @@ void paged_attn_varlen(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
   a.kv_lens = kv_lens.data_ptr<int>();
   a.q_lens = q_lens.data_ptr<int>();
   a.q_start = q_start.data_ptr<int>();
+  a.kv_fp8 = f8;
+  a.k_scale = (float)k_scale;
+  a.v_scale = (float)v_scale;
   shai::launch_flash_attn(a, stream());
 }
 
@@ -1940,8 +1957,8 @@ TORCH_LIBRARY(shai, m) {
   m.def("layernorm_mod(Tensor x, Tensor scale, Tensor shift, Tensor(a!) out, int rows_per_mod, float eps) -> ()");
   m.def("qk_norm_rope(Tensor(a!) x, Tensor? q_w, Tensor? k_w, Tensor? cos, Tensor? sin, int H, int D, int S, float eps) -> ()");
   m.def("conv2d(Tensor x, Tensor? x2, Tensor w, Tensor(a!) out, Tensor? bias, Tensor? bias2d, Tensor? residual, Tensor? in_scale, Tensor? in_shift, int in_act, int kh, int kw, int stride, int pad, bool upsample, int act, float res_alpha, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, bool up_phases=False) -> ()");
-  m.def("flash_attn(Tensor q, Tensor k, Tensor v, Tensor(a!) o, float scale, bool causal, int causal_offset, Tensor? kv_lens, Tensor? q_lens, Tensor? bias, Tensor? block_table) -> ()");
-  m.def("paged_attn_varlen(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor kv_lens, Tensor q_lens, Tensor q_start, int max_q, float scale, bool causal) -> ()");
+  m.def("flash_attn(Tensor q, Tensor k, Tensor v, Tensor(a!) o, float scale, bool causal, int causal_offset, Tensor? kv_lens, Tensor? q_lens, Tensor? bias, Tensor? block_table, float k_scale=1.0, float v_scale=1.0) -> ()");
+  m.def("paged_attn_varlen(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor kv_lens, Tensor q_lens, Tensor q_start, int max_q, float scale, bool causal, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor ctx_lens, Tensor(b!) ws, int num_splits, float scale, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("kv_write(Tensor k, Tensor v, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("kv_dequant_blocks(Tensor k_cache, Tensor v_cache, Tensor phys, Tensor(a!) k_out, Tensor(b!) v_out, float k_scale, float v_scale) -> ()");

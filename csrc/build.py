@@ -45,6 +45,8 @@ KERNEL_SRCS = ["kernels/norm.hip", "kernels/gemm.hip", "kernels/gemm_lds.hip", "
 # instantiations of the hand-scheduled split decode kernel sit near their register budget).  The kernels are picked
 # by name, not by the file a remark prints: that is the file the __global__ template is written in, a header.
 NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8",
+              # the native fp8 paged prefill attention (flash_v1.h's body with the fp8 format, D = 64 and 128)
+              "kernels/attention_kv8.hip": "flash_fwd_kernelINS_5KvFp8",
               # the fp4 tile GEMM holds up to 128 accumulators beside the widened fragments: every instantiation
               "kernels/gemm_fp4.hip": "gemm_fp4_kernel"}
 # per-source extra hipcc flags: gemm_w4's epilogue (256 accumulators x an activation) is larger than LLVM's

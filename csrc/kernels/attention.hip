@@ -19,6 +19,7 @@
 //   staged through LDS), followed by a split combine.
 #include "common.h"
 #include "decode_common.h"
+#include "flash_v1.h"   // flash_fwd_kernel: the v1 body, one for bf16 K/V (here) and the fp8 cache (attention_kv8.hip)
 #include "launchers.h"
 
 #include <algorithm>
@@ -28,254 +29,8 @@
 
 namespace shai {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef short s4v __attribute__((ext_vector_type(4)));
-
-constexpr float kLog2e = 1.4426950408889634f;
-constexpr float kRescaleThr = 8.f;   // flash_fwd deferred-max threshold (log2 units)
-
-template <int D>
-__device__ __forceinline__ int k_swz(int row, int ch) {
-  if constexpr (D == 128) return row * 128 + ((ch ^ (row & 15)) << 3);
-  else return row * 64 + ((ch ^ ((row >> 1) & 7)) << 3);
-}
-template <int D>
-__device__ __forceinline__ int v_swz(int row, int ch) {
-  if constexpr (D == 128) return row * 128 + ((ch ^ ((row & 3) << 2)) << 3);
-  else return row * 64 + ((ch ^ (((row >> 1) & 1) << 2)) << 3);
-}
-
-template <int D>
-__global__ void __launch_bounds__(256, 2) flash_fwd_kernel(const AttnArgs p) {
-  constexpr int KT = 64;                 // keys per tile
-  constexpr int CPR = D / 8;             // 16-byte chunks per row
-  constexpr int NST = KT * CPR / 256;    // chunks per thread per operand
-  constexpr int NS = D / 16;             // k-steps for QK^T
-  constexpr int ND = D / 32;             // 32-wide d blocks of O
-  extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
-  bf16_t* sK = smem;                     // [2][64*D]
-  bf16_t* sV = smem + 2 * KT * D;        // [2][64*D]
-
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int fr = lane & 31, fh = lane >> 5;
-  const int b = blockIdx.z, hq = blockIdx.y;
-  const int hk = hq / (p.Hq / p.Hkv);
-  const int q_len = p.q_lens ? p.q_lens[b] : p.Sq;
-  const int kv_len = p.kv_lens ? p.kv_lens[b] : p.Skv;
-  const int c_off = p.q_lens ? kv_len - q_len : p.causal_offset;
-  if ((int)blockIdx.x * 128 >= q_len) return;
-  const int q0 = blockIdx.x * 128;
-  const int qi = q0 + wid * 32 + fr;  // this lane's query
-
-  // ---- Q fragments (B operand of S^T = K Q^T): Q[qi][16 s + 8 fh .. +7]
-  bf16x8 qf[NS];
-  {
-    const bf16_t* qp = p.q + (p.q_start ? (long)p.q_start[b] * p.q_ts : (long)b * p.q_bs) +
-                        (long)min(qi, q_len - 1) * p.q_ts + (long)hq * D;
-#pragma unroll
-    for (int s = 0; s < NS; ++s) {
-      uint4_ v = *reinterpret_cast<const uint4_*>(qp + 16 * s + 8 * fh);
-      if (qi >= q_len) v = uint4_{0u, 0u, 0u, 0u};
-      qf[s] = __builtin_bit_cast(bf16x8, v);
-    }
-  }
-
-  // ---- number of key tiles this block needs
-  int kv_end = kv_len;
-  if (p.causal) kv_end = min(kv_end, q0 + 127 + c_off + 1);
-  const int ntiles = kv_end > 0 ? (kv_end + KT - 1) / KT : 0;
-
-  const bf16_t* kbase = p.k + (long)b * p.k_bs + (long)hk * D;
-  const bf16_t* vbase = p.v + (long)b * p.v_bs + (long)hk * D;
-
-  uint4_ rk[NST], rv[NST];
-  auto load_tile = [&](int t) {
-    const int key0 = t * KT;
-    const bf16_t* kb = kbase;
-    const bf16_t* vb = vbase;
-    long ts_k = p.k_ts, ts_v = p.v_ts;
-    int kbase_row = key0;
-    if (p.block_table) {
-      const int phys = p.block_table[(long)b * p.max_blocks + t];
-      kb = p.k + (long)phys * p.kc_bs + (long)hk * p.kc_hs;
-      vb = p.v + (long)phys * p.kc_bs + (long)hk * p.kc_hs;
-      ts_k = ts_v = D;
-      kbase_row = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < NST; ++i) {
-      const int id = tid + 256 * i;
-      const int row = id / CPR, ch = id % CPR;
-      const bool ok = key0 + row < kv_len;
-      rk[i] = ok ? *reinterpret_cast<const uint4_*>(kb + (long)(kbase_row + row) * ts_k + ch * 8) : uint4_{0u, 0u, 0u, 0u};
-      rv[i] = ok ? *reinterpret_cast<const uint4_*>(vb + (long)(kbase_row + row) * ts_v + ch * 8) : uint4_{0u, 0u, 0u, 0u};
-    }
-  };
-  auto store_tile = [&](int stage) {
-    bf16_t* ks = sK + stage * KT * D;
-    bf16_t* vs = sV + stage * KT * D;
-#pragma unroll
-    for (int i = 0; i < NST; ++i) {
-      const int id = tid + 256 * i;
-      const int row = id / CPR, ch = id % CPR;
-      *reinterpret_cast<uint4_*>(ks + k_swz<D>(row, ch)) = rk[i];
-      *reinterpret_cast<uint4_*>(vs + v_swz<D>(row, ch)) = rv[i];
-    }
-  };
-
-  float16_ o[ND];
-#pragma unroll
-  for (int d = 0; d < ND; ++d)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[d][r] = 0.f;
-  float m_run = -INFINITY, l_run = 0.f;
-  const float sl2 = p.scale * kLog2e;
-  const bf16_t* bias_row = p.bias ? p.bias + ((long)hq * p.Sq + min(qi, q_len - 1)) * p.Skv : nullptr;
-
-  if (ntiles > 0) {
-    load_tile(0);
-    store_tile(0);
-  }
-  __syncthreads();
-
-  // lane roles for the transposed V reads
-  const int g16 = lane >> 4, i16 = lane & 15;
-  const int tq = i16 >> 2, tp = i16 & 3;
-
-  for (int t = 0; t < ntiles; ++t) {
-    const int cur = t & 1;
-    if (t + 1 < ntiles) load_tile(t + 1);
-    const bf16_t* ks = sK + cur * KT * D;
-    const bf16_t* vs = sV + cur * KT * D;
-
-    // ---- S^T = K Q^T for two 32-key blocks
-    float16_ sacc[2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(ks + k_swz<D>(kb * 32 + fr, 2 * s + fh));
-        sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], sacc[kb], 0, 0, 0);
-      }
-    }
-    // ---- mask (+ bias), row max on raw scores, exp2 with the scale folded into one FMA
-    const int key0 = t * KT;
-    const bool need_mask = (key0 + KT > kv_len) || (p.causal && key0 + KT - 1 > q0 + c_off);
-    float mloc = -INFINITY;
-    if (bias_row) {  // T5 relative-position bias: additive in the natural-log domain
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-          sacc[kb][r] += (key < p.Skv ? bf2f(bias_row[key]) : 0.f) / p.scale;
-        }
-    }
-    if (need_mask) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int key = key0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-          const bool bad = key >= kv_len || (p.causal && key > qi + c_off);
-          sacc[kb][r] = bad ? -INFINITY : sacc[kb][r];
-        }
-    }
-    {  // 4 independent max chains (a single chain is 32 dependent v_max on the critical path)
-      float m4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) m4[r & 3] = fmaxf(m4[r & 3], sacc[kb][r]);
-      mloc = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-    }
-    mloc = fmaxf(mloc, __shfl_xor(mloc, 32, 64)) * sl2;   // scale > 0: max commutes with scaling
-    // Deferred max: keep the running max (and skip the O rescale) unless some row's max grew by more
-    // than kRescaleThr (log2 units) -- P is then bounded by 2^kRescaleThr instead of 1, which the bf16 P /
-    // fp32 O, l accumulators absorb; the decision precedes this tile's exponentials, so everything still at
-    // the old max is rescaled exactly once.
-    const float m_cand = fmaxf(m_run, mloc);
-    const bool grew = __any(m_cand > m_run + kRescaleThr);
-    const float m_keep = grew ? m_cand : m_run;
-    const float m_use = m_keep == -INFINITY ? 0.f : m_keep;
-    const float alpha = grew ? __builtin_amdgcn_exp2f(m_run - m_use) : 1.f;
-    m_run = m_keep;
-    float ls4[4] = {0.f, 0.f, 0.f, 0.f};  // independent partial row sums (ILP)
-    bf16x8 pf[2][2];
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float e = __builtin_amdgcn_exp2f(fmaf(sacc[kb][r], sl2, -m_use));
-        sacc[kb][r] = e;
-        ls4[r & 3] += e;
-      }
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8 v;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (__bf16)sacc[kb][8 * s + j];
-        pf[kb][s] = v;
-      }
-    }
-    const float lsum = (ls4[0] + ls4[1]) + (ls4[2] + ls4[3]);
-    l_run = l_run * alpha + lsum;
-    if (grew) {
-#pragma unroll
-      for (int d = 0; d < ND; ++d)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o[d][r] *= alpha;
-    }
-
-    // ---- O^T += V^T P^T
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-#pragma unroll
-      for (int kb = 0; kb < 2; ++kb) {
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-          const int r0 = kb * 32 + 16 * s + 4 * fh + tq;
-          const int col = d * 32 + 16 * (g16 & 1) + 4 * tp;
-          const int ch = col >> 3, half = (col >> 2) & 1;
-          const bf16_t* a0 = vs + v_swz<D>(r0, ch) + 4 * half;
-          const bf16_t* a1 = vs + v_swz<D>(r0 + 8, ch) + 4 * half;
-          const s4v t0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(a0));
-          const s4v t1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s4v*)(a1));
-          short8 vv;
-          vv[0] = t0[0]; vv[1] = t0[1]; vv[2] = t0[2]; vv[3] = t0[3];
-          vv[4] = t1[0]; vv[5] = t1[1]; vv[6] = t1[2]; vv[7] = t1[3];
-          o[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vv), pf[kb][s], o[d], 0, 0, 0);
-        }
-      }
-    }
-    if (t + 1 < ntiles) store_tile(cur ^ 1);
-    __syncthreads();
-  }
-
-  // ---- epilogue
-  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = l_tot > 0.f ? 1.f / l_tot : 0.f;
-  if (qi < q_len) {
-    bf16_t* op = p.o + (p.q_start ? (long)p.q_start[b] * p.o_ts : (long)b * p.o_bs) + (long)qi * p.o_ts +
-                 (long)hq * D;
-#pragma unroll
-    for (int d = 0; d < ND; ++d) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int dd = d * 32 + 8 * g + 4 * fh;
-        uint2_ w;
-        w[0] = pack2(o[d][4 * g] * inv, o[d][4 * g + 1] * inv);
-        w[1] = pack2(o[d][4 * g + 2] * inv, o[d][4 * g + 3] * inv);
-        *reinterpret_cast<uint2_*>(op + dd) = w;
-      }
-    }
-  }
-}
-
 // ----------------------------------------------------------------------------
-// flash64: the v1 structure above (4 waves x 32 queries, register-staged K/V, double-buffered swizzled
+// flash64: the v1 structure of flash_v1.h (4 waves x 32 queries, register-staged K/V, double-buffered swizzled
 // LDS, several workgroups per CU so that one wave's MFMAs overlap another's softmax) specialised for
 // D = 64 without bias / paged K/V -- every SD2.1 attention.  At D = 64 the loop is bound by VALU issue
 // (the softmax costs about what the 16 MFMAs of a 64-key tile do), so the VALU per tile is cut from
@@ -557,6 +312,10 @@ int set_flash128x2(int mode) {
 
 void launch_flash_attn(const AttnArgs& a, hipStream_t s) {
   static const bool v1_only = getenv("SHAI_FLASH_V1") != nullptr;  // A/B and tests: pin the v1 kernel
+  if (a.kv_fp8) {  // fp8 KV cache (paged): always the v1 body's fp8 format; the other kernels read bf16 K/V only
+    launch_flash_attn_kv8(a, s);
+    return;
+  }
   if (!v1_only && flash64_supported(a)) {  // D = 64 (every SD2.1 / ViT / BERT attention)
     launch_flash64(a, s);
     return;
@@ -571,8 +330,8 @@ void launch_flash_attn(const AttnArgs& a, hipStream_t s) {
   }
   dim3 grid((a.Sq + 127) / 128, a.Hq, a.B);
   const size_t lds = (size_t)4 * 64 * a.D * sizeof(bf16_t);
-  if (a.D == 128) flash_fwd_kernel<128><<<grid, 256, lds, s>>>(a);
-  else flash_fwd_kernel<64><<<grid, 256, lds, s>>>(a);
+  if (a.D == 128) flash_fwd_kernel<KvBf16<128>, 128><<<grid, 256, lds, s>>>(a);
+  else flash_fwd_kernel<KvBf16<64>, 64><<<grid, 256, lds, s>>>(a);
 }
 
 // ----------------------------------------------------------------------------

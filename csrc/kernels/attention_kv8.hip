@@ -1,8 +1,10 @@
-// FP8 (OCP e4m3fn) paged KV cache for gfx950: the cache writers and the block widener that lets the bf16 prefill
-// kernels run over a bf16 scratch copy of the blocks a step needs.  (Decode attention reads the codes directly: the
+// FP8 (OCP e4m3fn) paged KV cache for gfx950: the cache writers, the native paged prefill attention (the fp8
+// instantiations of flash_v1.h's kernel body) and the block widener that lets the bf16 prefill kernels run over a
+// bf16 scratch copy of the blocks a step needs (the "widen" route).  (Decode attention reads the codes directly: the
 // split kernel of decode_common.h with its KvFp8 format, where the quantisation rule and its helpers live.)
 #include "common.h"
 #include "decode_common.h"
+#include "flash_v1.h"
 #include "launchers.h"
 
 namespace shai {
@@ -178,6 +180,18 @@ void launch_kv_dequant_blocks(const uint8_t* k_cache, const uint8_t* v_cache, co
   if (blocks > 8192) blocks = 8192;
   kv_dequant_blocks_kernel<<<(int)blocks, 256, 0, s>>>(k_cache, v_cache, phys, n, block_elems, k_out, v_out, k_scale,
                                                        v_scale);
+}
+
+// ----------------------------------------------------------------------------
+// Native fp8 paged prefill attention: the v1 flash body of flash_v1.h with the KvFp8 format -- the codes are loaded
+// 16 per chunk, widened once per tile at staging and attended from the same swizzled bf16 LDS tiles, so no scratch
+// copy of the cache exists.  Padded ([B, S] q with a block table) and packed (q_start) layouts, causal, GQA.
+// ----------------------------------------------------------------------------
+void launch_flash_attn_kv8(const AttnArgs& a, hipStream_t s) {
+  dim3 grid((a.Sq + 127) / 128, a.Hq, a.B);
+  const size_t lds = (size_t)4 * 64 * a.D * sizeof(bf16_t);
+  if (a.D == 128) flash_fwd_kernel<KvFp8<128>, 128><<<grid, 256, lds, s>>>(a);
+  else flash_fwd_kernel<KvFp8<64>, 64><<<grid, 256, lds, s>>>(a);
 }
 
 }  // namespace shai

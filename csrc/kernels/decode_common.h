@@ -89,6 +89,9 @@ struct KvBf16 {
   static __device__ __forceinline__ float v_f32(E v) { return bf2f(v); }
   static __device__ __forceinline__ float qk_scale(const DecodeAttnArgs& p) { return p.scale; }
   static __device__ __forceinline__ float out_scale(const DecodeAttnArgs&) { return 1.f; }
+  // (the paged flash kernel of flash_v1.h takes the same two from its own arguments)
+  static __device__ __forceinline__ float qk_scale(const AttnArgs& p) { return p.scale; }
+  static __device__ __forceinline__ float out_scale(const AttnArgs&) { return 1.f; }
   // roped k rounded to bf16, as the cache stores it; v is bf16 already: both attended and stored as they are
   static __device__ __forceinline__ void new_k(const DecodeAttnArgs&, float x0, float x1, float c, float sn,
                                                float& k0, float& k1, uint32_t&) {
@@ -168,6 +171,8 @@ struct KvFp8 {
   static __device__ __forceinline__ float v_f32(E v) { return __builtin_amdgcn_cvt_f32_fp8((int)v, 0); }
   static __device__ __forceinline__ float qk_scale(const DecodeAttnArgs& p) { return p.scale * p.k_scale; }
   static __device__ __forceinline__ float out_scale(const DecodeAttnArgs& p) { return p.v_scale; }
+  static __device__ __forceinline__ float qk_scale(const AttnArgs& p) { return p.scale * p.k_scale; }
+  static __device__ __forceinline__ float out_scale(const AttnArgs& p) { return p.v_scale; }
   // roped k rounded to bf16 and then to its fp8 code, v to its code -- the values every later reader of the cache
   // will see.  The K rotation is kv8_rope_k, not the bf16 expression: the stored codes are checked exactly
   static __device__ __forceinline__ void new_k(const DecodeAttnArgs& p, float x0, float x1, float c, float sn,

@@ -265,8 +265,15 @@ struct AttnArgs {
   const int* block_table;   // optional [B, max_blocks]
   int max_blocks;
   long kc_bs, kc_hs;        // cache strides: block stride, head stride (elements); token stride = D
+  // fp8 (OCP e4m3fn) paged cache (kv_fp8): k / v point at one-byte codes, value = float(code) * scale; needs a
+  // block table, has no bias path.  (Appended: the other fields keep their offsets in the kernels' arguments)
+  float k_scale, v_scale;
+  int kv_fp8;
 };
+// an fp8 cache (kv_fp8) always takes launch_flash_attn_kv8; bf16 K/V the routing of attention.hip
 void launch_flash_attn(const AttnArgs& a, hipStream_t s);
+// the v1 body with the fp8 cache format (attention_kv8.hip): paged prefill attention straight from the codes
+void launch_flash_attn_kv8(const AttnArgs& a, hipStream_t s);
 // v2 (attention2.hip): 8-wave ping-pong, LDS-DMA K/V ring; launch_flash_attn dispatches to it when supported
 bool flash2_supported(const AttnArgs& a);
 bool flash64_supported(const AttnArgs& a);

@@ -85,7 +85,9 @@ def main(argv=None):
            "ttft_ms": round(1000 * ttft, 1), "prefill_tok_per_s": round(P / ttft, 1),
            "tpot_ms_long": round(1000 * tpot, 3), "steady_tpot_ms_background": round(1000 * steady_tpot, 3),
            "prefill_steps": steps_prefill, "background_tokens_during_prefill": int(bg_during),
-           "gen_len": n_long}
+           "gen_len": n_long, "kv_cache_dtype": eng.kv_cache_dtype,
+           "kv_prefill": eng.kv_prefill if eng.kv_fp8 else None,   # (SHAI_KV_CACHE_DTYPE / SHAI_KV8_PREFILL)
+           "kv_blocks_budget": eng.kv_blocks_budget, "kv_scratch_bytes": int(eng.kv_scratch_bytes)}
     print(json.dumps(res), flush=True)
     return res
 

@@ -352,11 +352,18 @@ class LLMEngine:
                  enable_prefix_caching: bool = True, prefill_chunk: Optional[int] = None,
                  quantization: Optional[str] = None, async_decode: Optional[bool] = None,
                  packed_prefill: bool = True, mixed_steps: bool = True, kv_cache_dtype: Optional[str] = None,
-                 k_scale: float = 1.0, v_scale: float = 1.0, kv_scratch_blocks: Optional[int] = None):
+                 k_scale: float = 1.0, v_scale: float = 1.0, kv_scratch_blocks: Optional[int] = None,
+                 kv_prefill: Optional[str] = None):
         from ..models.mllama import MllamaConfig, MllamaForConditionalGeneration
         from ..runtime import BlockManager
         self.kv_cache_dtype, self.kv_dtype = resolve_kv_cache_dtype(kv_cache_dtype)
         self.kv_fp8 = self.kv_dtype == torch.float8_e4m3fn
+        # fp8 cache, prefill / mixed steps: "native" (the paged kernel reads the codes; no scratch) or "widen"
+        # (the bf16 scratch + rounds below); None reads SHAI_KV8_PREFILL (unset: widen).  Unused with a bf16 cache.
+        self.kv_prefill = ops.resolve_kv_prefill(kv_prefill)
+        if self.kv_fp8 and self.kv_prefill == "native" and kv_scratch_blocks is not None:
+            raise ValueError("kv_prefill='native' allocates no dequantisation scratch: kv_scratch_blocks="
+                             f"{kv_scratch_blocks} has no meaning with it")
         self.mcfg = cfg if isinstance(cfg, MllamaConfig) else None
         if self.kv_fp8 and self.mcfg is not None:
             raise NotImplementedError("kv_cache_dtype=fp8 is not supported yet for multimodal (mllama) models: the "
@@ -393,10 +400,10 @@ class LLMEngine:
         self.max_cross_blocks = (self.cross_tokens + KV_BLOCK - 1) // KV_BLOCK
         hk = self.model.kv_heads_local
         per_seq = self.max_blocks + self.max_cross_blocks
-        # fp8 cache: per-layer scalar scales (value = code * scale), the same on every TP rank, and the bf16
-        # scratch the prefill / mixed steps widen blocks into (one layer at a time, reused by every layer).  Its
-        # capacity is fixed here -- at least one full max_model_len sequence plus a block -- and comes out of the
-        # memory budget before the block pool is sized.
+        # fp8 cache: per-layer scalar scales (value = code * scale), the same on every TP rank, and -- on the
+        # "widen" prefill route only -- the bf16 scratch the prefill / mixed steps widen blocks into (one layer at a
+        # time, reused by every layer).  Its capacity is fixed here -- at least one full max_model_len sequence plus
+        # a block -- and comes out of the memory budget before the block pool is sized; the "native" route has none.
         self.k_scales = [float(k_scale)] * cfg.num_hidden_layers
         self.v_scales = [float(v_scale)] * cfg.num_hidden_layers
         self.kv_scratch = None
@@ -404,6 +411,7 @@ class LLMEngine:
         scratch_bytes = 0
         if self.kv_fp8:
             self.set_kv_scales(self.k_scales, self.v_scales)
+        if self.kv_fp8 and self.kv_prefill == "widen":
             want = kv_scratch_blocks if kv_scratch_blocks is not None else max(
                 self.max_blocks + 1, (prefill_token_budget + KV_BLOCK - 1) // KV_BLOCK + max_num_seqs)
             self.kv_scratch_blocks = max(int(want), self.max_blocks + 1)
@@ -466,9 +474,23 @@ class LLMEngine:
             layer.self_attn.k_scale, layer.self_attn.v_scale = ks, vs
 
     def _attach_kv_rounds(self, batch: Batch, bt, lens, qlens, qstart, S: int) -> None:
-        """fp8 cache: plan this prefill step's dequant + attention rounds from the host block lists (no device
-        sync) and hand the scratch to the model."""
-        if not self.kv_fp8 or self.device.type != "cuda":
+        """fp8 cache, "widen" route: plan this prefill step's dequant + attention rounds from the host block lists
+        (no device sync) and hand the scratch to the model.  The "native" route plans nothing."""
+        if not self.kv_fp8:
+            return
+        batch.kv_prefill = self.kv_prefill
+        if self.kv_prefill == "native":
+            # the kernel walks the step's own block table.  Only the launch is split where one-token rows (the
+            # decode rows, packed last) follow the prefill chunks, so that they are not dispatched the chunks'
+            # query tiles
+            ql = np.asarray(qlens)
+            ones = 0
+            while qstart is not None and ones < len(ql) and ql[len(ql) - 1 - ones] == 1:
+                ones += 1
+            if 0 < ones < len(ql):
+                batch.q_groups = [(0, len(ql) - ones, int(ql[:len(ql) - ones].max())), (len(ql) - ones, ones, 1)]
+            return
+        if self.device.type != "cuda":
             return
         batch.kv_scratch = self.kv_scratch
         batch.kv_rounds = ops.build_kv_rounds(bt, lens, qlens, qstart, self.kv_scratch_blocks, self.device, S)
@@ -899,7 +921,7 @@ def bench_decode_throughput(args, rank, world):
     kvd = getattr(args, "kv_cache_dtype", None)
     eng = LLMEngine(cfg, device=f"cuda:{torch.cuda.current_device()}", max_num_seqs=max(B, 1),
                     max_model_len=P + G + 64, enable_prefix_caching=False, quantization=quant,
-                    kv_cache_dtype=kvd)
+                    kv_cache_dtype=kvd, kv_prefill=getattr(args, "kv_prefill", None))
     params = SamplingParams(temperature=0.7, top_k=50, top_p=0.9, max_tokens=G, ignore_eos=True)
     rng = np.random.default_rng(0)
     prompts = lambda: [rng.integers(10, cfg.vocab_size - 10, P).tolist() for _ in range(B)]

@@ -162,6 +162,12 @@ class Batch:
     # every layer) and the host-built dequant + attention rounds (ops.build_kv_rounds); None with a bf16 cache
     kv_scratch: Optional[tuple] = None
     kv_rounds: Optional[list] = None
+    # fp8 KV cache: the engine's prefill-attention route ("native": the paged kernel reads the codes, no scratch and
+    # no rounds; "widen": the two fields above); None leaves the choice to ops.resolve_kv_prefill
+    kv_prefill: Optional[str] = None
+    # native route, packed steps: launch groups (first sequence, count, largest q_len) -- the prefill chunks, then
+    # the decode rows that joined the step (see ops.paged_attention_varlen); None = one launch
+    q_groups: Optional[list] = None
 
 
 class LlamaAttention(nn.Module):
@@ -204,11 +210,13 @@ class LlamaAttention(nn.Module):
         if batch.is_prefill and batch.q_start is not None:
             o = ops.paged_attention_varlen(q, k_cache, v_cache, batch.block_table, batch.ctx_lens, batch.q_lens,
                                            batch.q_start, batch.S, self.scale, k_scale=ks, v_scale=vs,
-                                           scratch=batch.kv_scratch, rounds=batch.kv_rounds).view(T, h * hd)
+                                           scratch=batch.kv_scratch, rounds=batch.kv_rounds,
+                                           kv_prefill=batch.kv_prefill, q_groups=batch.q_groups).view(T, h * hd)
         elif batch.is_prefill:
             o = ops.paged_attention(q.view(batch.B, batch.S, h, hd), k_cache, v_cache, batch.block_table,
                                     batch.ctx_lens, batch.q_lens, self.scale, causal=True, k_scale=ks, v_scale=vs,
-                                    scratch=batch.kv_scratch, rounds=batch.kv_rounds).view(T, h * hd)
+                                    scratch=batch.kv_scratch, rounds=batch.kv_rounds,
+                                    kv_prefill=batch.kv_prefill).view(T, h * hd)
         else:
             o = ops.decode_attention(q, k_cache, v_cache, batch.block_table, batch.ctx_lens, self.scale,
                                      num_splits=batch.num_splits, k_scale=ks, v_scale=vs).view(T, h * hd)

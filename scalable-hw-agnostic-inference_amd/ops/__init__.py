@@ -28,7 +28,7 @@ __all__ = [
     "softmax_", "embedding", "token_feedback", "decode_attention_rope", "decode_attention_rope_qkv", "gemm_partials", "quantize_fp8_rows", "dequant_fp8", "quantize_mxfp4", "dequant_mxfp4", "mxfp4_pack", "mxfp4_unpack", "is_mxfp4", "quant_rows_fp8", "gemm_f8", "pack_conv_weight", "pack_up2_phase_weight", "linear_wslices", "unpack_conv_weight", "act_id", "ACT_NONE", "ACT_SILU", "ACT_GELU",
     "ACT_GELU_TANH", "ACT_QUICK_GELU", "ACT_RELU", "decode_splits", "set_decode_wb",
     "paged_attention_varlen", "rope_qkv_cache", "quantize_kv_fp8", "dequant_kv_fp8", "kv_dequant_blocks",
-    "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE",
+    "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE", "resolve_kv_prefill", "KV_PREFILL_ROUTES",
 ]
 
 
@@ -697,6 +697,20 @@ def build_kv_rounds(block_table, kv_lens, q_lens, q_start, capacity: int, device
     return rounds
 
 
+KV_PREFILL_ROUTES = ("widen", "native")
+
+
+def resolve_kv_prefill(kv_prefill: Optional[str] = None) -> str:
+    """Route of the prefill attention over an fp8 cache: ``native`` reads the codes in the paged flash kernel (one
+    launch: no scratch, no rounds, no host read of device metadata); ``widen`` copies the blocks a step needs into
+    a bf16 scratch and runs the bf16 kernel on it.  None reads ``SHAI_KV8_PREFILL`` (unset: widen)."""
+    name = kv_prefill if kv_prefill is not None else os.environ.get("SHAI_KV8_PREFILL")
+    name = "widen" if name is None or str(name).strip() == "" else str(name).strip().lower()
+    if name not in KV_PREFILL_ROUTES:
+        raise ValueError(f"kv_prefill={name!r}: supported: " + ", ".join(KV_PREFILL_ROUTES))
+    return name
+
+
 def _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q, scale, causal, k_scale, v_scale,
                scratch, rounds):
     """Prefill attention over an fp8 cache: widen the blocks a round needs into the bf16 scratch, run the bf16
@@ -734,13 +748,22 @@ def _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q
 
 
 def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=None, causal=True,
-                    k_scale: float = 1.0, v_scale: float = 1.0, scratch=None, rounds=None):
-    """Prefill attention over a paged KV cache (64-token blocks).  An fp8 cache (``k_scale`` / ``v_scale``) is
-    widened block-wise into the bf16 ``scratch`` pair ([capacity, Hkv, 64, D]) in one or more ``rounds``."""
+                    k_scale: float = 1.0, v_scale: float = 1.0, scratch=None, rounds=None,
+                    kv_prefill: Optional[str] = None):
+    """Prefill attention over a paged KV cache (64-token blocks).  An fp8 cache (``k_scale`` / ``v_scale``) takes
+    the route ``kv_prefill`` (:func:`resolve_kv_prefill`; ignored for a bf16 cache): ``native`` is one launch of the
+    paged kernel on the codes (``scratch`` / ``rounds`` are ignored); ``widen`` copies the blocks into the bf16
+    ``scratch`` pair ([capacity, Hkv, 64, D]) in one or more ``rounds``.  On the CPU both run the reference."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    native = _kv8(k_cache, v_cache) and resolve_kv_prefill(kv_prefill) == "native"
     if not _gpu(q):
         return ref.paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale, causal, k_scale, v_scale)
+    if native:
+        o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        _K().flash_attn(q, k_cache, v_cache, o, float(scale), bool(causal), 0, _i32(kv_lens), _i32(q_lens), None,
+                        _i32(block_table), float(k_scale), float(v_scale))
+        return o
     if _kv8(k_cache, v_cache):
         return _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, None, q.shape[1], scale, causal,
                           k_scale, v_scale, scratch, rounds)
@@ -751,14 +774,30 @@ def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=Non
 
 
 def paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q: int, scale=None,
-                           causal=True, k_scale: float = 1.0, v_scale: float = 1.0, scratch=None, rounds=None):
+                           causal=True, k_scale: float = 1.0, v_scale: float = 1.0, scratch=None, rounds=None,
+                           kv_prefill: Optional[str] = None, q_groups=None):
     """Packed (varlen) prefill attention over a paged KV cache: q [T, Hq, D] holds every sequence's new tokens
-    back to back (sequence b = rows q_start[b] .. + q_lens[b] - 1), so no padding rows are computed."""
+    back to back (sequence b = rows q_start[b] .. + q_lens[b] - 1), so no padding rows are computed.  An fp8 cache
+    takes the route ``kv_prefill`` as in :func:`paged_attention`.  ``q_groups`` (native route; host integers): launch
+    groups ``(first sequence, count, largest q_len)`` that partition the step's sequences -- the engine's prefill
+    chunks and the decode rows that joined them -- instead of one launch sized by ``max_q``."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    native = _kv8(k_cache, v_cache) and resolve_kv_prefill(kv_prefill) == "native"
     if not _gpu(q):
         return ref.paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, scale, causal,
                                           k_scale, v_scale)
+    if native:
+        o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        bt, kl, ql, qs = _i32(block_table), _i32(kv_lens), _i32(q_lens), _i32(q_start)
+        # the grid is (max_q / 128 query tiles) x heads x sequences: one launch per group keeps a step's decode rows
+        # (q_len 1) from being dispatched a long prompt's worth of query tiles that exit at once
+        for first, n, mq in (q_groups if q_groups else [(0, bt.shape[0], max_q)]):
+            if n > 0:
+                _K().paged_attn_varlen(q, k_cache, v_cache, o, bt[first:first + n], kl[first:first + n],
+                                       ql[first:first + n], qs[first:first + n], int(mq), float(scale), bool(causal),
+                                       float(k_scale), float(v_scale))
+        return o
     if _kv8(k_cache, v_cache):
         return _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q, scale, causal, k_scale,
                           v_scale, scratch, rounds)

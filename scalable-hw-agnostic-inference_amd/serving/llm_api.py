@@ -19,7 +19,9 @@ deployment of the reference's bitsandbytes ``load_in_4bit`` models) and
 kv_cache_dtype (``auto`` / ``bf16``, or ``fp8`` / ``fp8_e4m3``: OCP e4m3fn KV
 cache with scalar k/v scales -- half the KV bytes per decode step, twice the
 tokens per block pool; every TP rank reads the same file, so the relaunched
-ranks build the same cache).
+ranks build the same cache) with kv_prefill (``widen``, the default, or
+``native``: the prefill attention reads the fp8 cache directly and the engine
+holds no bf16 scratch).
 
 Tensor parallelism (``tensor_parallel_size: N``, app/vllm_model_api.py:127-129 with
 cova/mllama-32-11b-vllm-trn1-config.yaml:9): the worker runs as N processes, one
@@ -71,7 +73,7 @@ def build_engine(env: ServerEnv, vc: Optional[dict] = None):
                     max_num_seqs=int(vc.get("max_num_seqs", 64)),
                     max_model_len=int(vc.get("max_model_len", min(8192, text.max_position_embeddings))),
                     enable_prefix_caching=True, quantization=vc.get("quantization"),
-                    kv_cache_dtype=vc.get("kv_cache_dtype"))
+                    kv_cache_dtype=vc.get("kv_cache_dtype"), kv_prefill=vc.get("kv_prefill"))
     import torch
     with torch.inference_mode():
         # every decode batch bucket (sampled and all-greedy) captured before the first request

@@ -3,7 +3,8 @@
 (hipBLASLt GEMM, MIOpen conv, SDPA) on the same random bf16 inputs.
 
 python tools/bench_kernels.py [--only gemm,conv,attn,norm] [--json out.json]
-(--only kv8: decode attention over bf16 vs fp8 KV caches)
+(--only kv8: decode attention over bf16 vs fp8 KV caches, then prefill attention over an fp8 cache by the native
+and the widen route; SHAI_KV8_ROWS=decode|prefill keeps one of the two groups)
 """
 import argparse
 import json
@@ -434,27 +435,9 @@ def bench_kv8(rows):
     shapes = [(64, 192), (64, 1024), (256, 1024), (1, 65536)]
     if os.environ.get("SHAI_KV8_SHAPES"):  # e.g. "64x192,1x65536": batch x context
         shapes = [tuple(int(v) for v in t.split("x")) for t in os.environ["SHAI_KV8_SHAPES"].split(",")]
-
-    def replayer(fn, iters):
-        fn()
-        torch.cuda.synchronize()
-        s = torch.cuda.Stream()
-        with torch.cuda.stream(s):
-            fn()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, stream=s):
-                for _ in range(iters):
-                    fn()
-        torch.cuda.synchronize()
-
-        def run():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            g.replay()
-            e1.record()
-            torch.cuda.synchronize()
-            return e0.elapsed_time(e1) / iters * 1e3   # us per call
-        return run
+    if os.environ.get("SHAI_KV8_ROWS", "all") == "prefill":   # only the prefill rows below
+        shapes = []
+    replayer = _replayer
 
     for B, ctx in shapes:
         nblk = (ctx + 63) // 64
@@ -498,6 +481,112 @@ def bench_kv8(rows):
         r["fp8_speedup"] = r["bf16_us"] / r["fp8_us"]
         rows.append(r)
         del caches, k16, v16
+        torch.cuda.empty_cache()
+    if os.environ.get("SHAI_KV8_ROWS", "all") != "decode":
+        bench_kv8_prefill(rows)
+
+
+def _replayer(fn, iters):
+    """`iters` calls of fn captured into one HIP graph; the returned run() replays it once and gives us per call."""
+    fn()
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        fn()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            for _ in range(iters):
+                fn()
+    torch.cuda.synchronize()
+
+    def run():
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / iters * 1e3   # us per call
+    return run
+
+
+# packed prefill steps over an fp8 cache: name -> (cached tokens, new tokens) per sequence
+KV8_PREFILL_SHAPES = {
+    "a: 8 x 1024 fresh prompts": ([0] * 8, [1024] * 8),
+    "b: 8192 new on 8192 cached": ([8192], [8192]),
+    "c: one 4096 prompt + 256 decode rows @1024": ([0] + [1023] * 256, [4096] + [1] * 256),
+    "d: one 192 prompt + 64 decode rows @192": ([0] + [191] * 64, [192] + [1] * 64),
+}
+
+
+def bench_kv8_prefill(rows):
+    """Packed prefill attention (Mistral-7B layer: 32 q / 8 KV heads, D 128) over an fp8 paged cache by the two
+    routes of ``kv_prefill``: native (one launch on the codes) against widen (``kv_dequant_blocks`` into a bf16
+    scratch sized for the step -- one round, planned ahead as the engine does -- plus the bf16 kernel).  Same
+    method as the decode rows above: HIP-graph replays, the routes alternating in three repetitions (min / max),
+    calls rotating over at least 1 GB of cache copies.  Bytes are the step's compulsory traffic: every attended
+    cache element once (1 byte; the widen route adds a 2-byte write and a 2-byte read of it) plus q and o."""
+    h, hk, D = 32, 8, 128
+    shapes = KV8_PREFILL_SHAPES
+    if os.environ.get("SHAI_KV8_PREFILL_SHAPES"):   # e.g. "a,d"
+        keep = os.environ["SHAI_KV8_PREFILL_SHAPES"].split(",")
+        shapes = {k: v for k, v in shapes.items() if k[0] in keep}
+    for name, (n_cached, n_new) in shapes.items():
+        ctx = [c + n for c, n in zip(n_cached, n_new)]
+        need = [(c + 63) // 64 for c in ctx]
+        nblk, B, T = sum(need), len(ctx), sum(n_new)
+        per_copy = nblk * hk * 64 * D * 2          # fp8 K + V bytes of one copy's blocks
+        ncopy = max(2, -(-(1 << 30) // per_copy))
+        pool = ncopy * nblk + 8
+        kc, vc = ops.quantize_kv_fp8(rnd(pool, hk, 64, D), 0.5), ops.quantize_kv_fp8(rnd(pool, hk, 64, D), 2.0)
+        perm = torch.randperm(pool)[:ncopy * nblk].view(ncopy, nblk).int()
+        bt_host = torch.zeros(ncopy, B, max(need), dtype=torch.int32)
+        o = 0
+        for b, n in enumerate(need):
+            bt_host[:, b, :n] = perm[:, o:o + n]
+            o += n
+        bts = bt_host.cuda()
+        kv_lens = torch.tensor(ctx, dtype=torch.int32)
+        q_lens = torch.tensor(n_new, dtype=torch.int32)
+        q_start = torch.cumsum(q_lens, 0, dtype=torch.int32) - q_lens
+        plans = [ops.build_kv_rounds(bt_host[i].numpy(), kv_lens.numpy(), q_lens.numpy(), q_start.numpy(), nblk, "cuda")
+                 for i in range(ncopy)]
+        assert all(len(p) == 1 for p in plans)
+        scratch = (torch.empty(nblk, hk, 64, D, device="cuda", dtype=torch.bfloat16),
+                   torch.empty(nblk, hk, 64, D, device="cuda", dtype=torch.bfloat16))
+        kvl, ql, qs = kv_lens.cuda(), q_lens.cuda(), q_start.cuda()
+        q = rnd(T, h, D)
+        iters = ncopy
+        # "native2": the engine's launch split of a mixed step -- the prompts, then the one-token rows behind them
+        ones = next((i for i, n in enumerate(reversed(n_new)) if n != 1), B)
+        groups = [(0, B - ones, max(n_new[:B - ones])), (B - ones, ones, 1)] if 0 < ones < B else None
+        routes = ("widen", "native") + (("native2",) if groups else ())
+        state = {route: 0 for route in routes}
+
+        def fn(route):
+            i = state[route] % ncopy
+            state[route] += 1
+            return ops.paged_attention_varlen(q, kc, vc, bts[i], kvl, ql, qs, max(n_new), k_scale=0.5, v_scale=2.0,
+                                              scratch=scratch, rounds=plans[i], kv_prefill=route[:6],
+                                              q_groups=groups if route == "native2" else None)
+        outs = [fn(route) for route in routes]   # (state: all read copy 0)
+        assert all(torch.equal(outs[0], x) for x in outs[1:])
+        runs = {route: _replayer(lambda route=route: fn(route), iters) for route in routes}
+        t = {route: [] for route in runs}
+        for _ in range(3):
+            for route, run in runs.items():
+                t[route].append(min(run() for _ in range(2)))
+        elems = sum(ctx) * hk * D * 2               # attended K + V cache elements
+        qo = 2 * T * h * D * 2
+        byt = {"native": elems + qo, "native2": elems + qo, "widen": 5 * elems + qo}
+        r = dict(op="prefill_attn_kv8", shape=name, tokens=T, blocks=nblk, copies=ncopy)
+        for route in routes:
+            r[f"{route}_us"] = min(t[route])
+            r[f"{route}_us_max"] = max(t[route])
+            r[f"{route}_MB"] = byt[route] / 1e6
+            r[f"{route}_GBps"] = byt[route] / 1e9 / (min(t[route]) / 1e6)
+        r["native_speedup"] = r["widen_us"] / min(r["native_us"], r.get("native2_us", float("inf")))
+        rows.append(r)
+        del kc, vc, scratch, runs
         torch.cuda.empty_cache()
 
 

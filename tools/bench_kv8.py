@@ -7,6 +7,7 @@ is named ``<kv>+<weights>``: bf16+bf16, fp8+bf16, bf16+mxfp4, fp8+mxfp4.
 
 python tools/bench_kv8.py [--llm-model mistral_7b] [--batch 256] [--prompt-len 1024] [--gen-len 64]
                           [--steps 1] [--warmup 1] [--variants bf16+bf16,fp8+bf16,bf16+mxfp4,fp8+mxfp4]
+                          [--kv-prefill widen|native]   (the fp8 variants' prefill attention route)
 """
 import argparse
 import json
@@ -29,15 +30,18 @@ def child(a):
         init(self, *args, **kw)
         seen.update(num_kv_blocks=int(self.num_kv_blocks), kv_blocks_budget=self.kv_blocks_budget,
                     kv_bytes=int(self.kv_bytes),
-                    kv_scratch_bytes=int(self.kv_scratch_bytes), kv_dtype=str(self.kv_buf.dtype))
+                    kv_scratch_bytes=int(self.kv_scratch_bytes), kv_dtype=str(self.kv_buf.dtype),
+                    kv_prefill=self.kv_prefill)
     llm.LLMEngine.__init__ = recording_init
     kv, w = a.child.split("+")
     ns = argparse.Namespace(batch=a.batch, prompt_len=a.prompt_len, gen_len=a.gen_len, steps=a.steps,
                             warmup=a.warmup, tp=1, llm_model=a.llm_model, quantization=None if w == "bf16" else w,
-                            kv_cache_dtype=kv)
+                            kv_cache_dtype=kv, kv_prefill=a.kv_prefill)
     with torch.inference_mode():
         r = llm.bench_decode_throughput(ns, 0, 1)
     r["variant"] = a.child
+    if kv == "fp8":
+        r["kv_prefill"] = seen.get("kv_prefill")
     r.update(seen)
     r["kv_gb"] = round(seen.get("kv_bytes", 0) / 1e9, 2)
     print("BENCH_KV8 " + json.dumps(r), flush=True)
@@ -53,6 +57,8 @@ def main():
     ap.add_argument("--steps", type=int, default=1)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--variants", default=",".join(VARIANTS))
+    ap.add_argument("--kv-prefill", default=None, choices=["widen", "native"],
+                    help="prefill attention route of the fp8-cache variants (default: SHAI_KV8_PREFILL, else widen)")
     ap.add_argument("--timeout", type=int, default=900, help="seconds per variant")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -64,6 +70,8 @@ def main():
         cmd = [sys.executable, os.path.abspath(__file__), "--child", v, "--llm-model", a.llm_model,
                "--batch", str(a.batch), "--prompt-len", str(a.prompt_len), "--gen-len", str(a.gen_len),
                "--steps", str(a.steps), "--warmup", str(a.warmup)]
+        if a.kv_prefill:
+            cmd += ["--kv-prefill", a.kv_prefill]
         try:
             p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=a.timeout)
         except subprocess.TimeoutExpired:
