@@ -72,7 +72,7 @@ std::unordered_map<std::string, Choice> g_tuned;
 
 bool lib_supported(const shai::GemmArgs& g) {
   return g.conv == 0 && !g.row_mr && g.batch <= 1 && !g.w_slice_rows && !g.glu && g.act == 0 && !g.bias2d && !g.gate &&
-         !g.rms && !shai::quantized_w(g) &&
+         !g.rms && !shai::quantized_w(g) && g.res_rows == 0 &&
          !g.A2 && !g.in_scale && g.alpha == 1.f && !(g.bias && g.residual) &&
          (!g.residual || (g.res_alpha == 1.f && g.residual == g.C && g.ldr == g.ldc)) &&
          g.lda >= g.K && g.ldw >= g.K && g.ldc >= g.N;
@@ -87,6 +87,8 @@ std::string gemm_key(const shai::GemmArgs& g) {
   // a folded-LayerNorm GEMM (row_mr) runs only unsplit on v4: it tunes and caches apart from the plain problem
   return std::string(buf) + (g.rms ? "|rms" : "") + (g.w_scale ? "|fp8w" : "") + (g.w_mx_scale ? "|mxfp4w" : "") + (g.row_mr ? "|ln" : "") +
          (g.w_slice_rows ? "|wslice" + std::to_string(g.w_slice_rows) : "") +
+         // a broadcast residual races only the kernels that wrap it: its winner is kept apart from the plain problem's
+         (g.res_rows ? "|rr" : "") +
          (lib_supported(g) && !g.residual ? "|lib" : "");
 }
 
@@ -196,8 +198,9 @@ inline bool is_fp4_tile(int cfg) {
 // config, never "whichever kernel happens to be numbered highest".  The v2 128x64 tile (cfg 4) runs every
 // problem the v2 kernel accepts; folded-LayerNorm problems (row_mr) are applied only by the v4 epilogue
 // (cfg 9 / 10, 256 x 256 / 256 x 320).  tests/test_gemm3_gpu.py forces each of these.
+// A broadcast residual (res_rows) below 256-row multiples is taken by the W-stationary kernel alone (the last config).
 Choice fallback_choice(const shai::GemmArgs& g) {
-  for (int c : {4, 9, 10})
+  for (int c : {4, 9, 10, shai::gemm2_num_cfgs() - 1})
     if (shai::gemm2_cfg_supported(g, c)) return Choice{c, 1};
   return Choice{4, 1};
 }
@@ -305,6 +308,9 @@ void launch_choice(const shai::GemmArgs& g, const Tensor& like, Choice c) {
   }
   // a choice reused from another row count of the same bucket must still fit this problem
   if (!shai::gemm2_cfg_supported(g, c.cfg)) c = fallback_choice(g);
+  // a kernel that ignores the field would read the residual past its end (resolve_res_rows sets it only when a
+  // config takes it)
+  SHAI_CHECK(g.res_rows == 0 || shai::gemm2_cfg_supported(g, c.cfg), "no kernel for this broadcast-residual problem");
   Tensor ws;
   float* wsp = nullptr;
   if (c.splits > 1) {
@@ -612,6 +618,35 @@ void kv8_scales(shai::DecodeAttnArgs& a, double k_scale, double v_scale) {
   a.v_scale = (float)v_scale;
   a.k_inv = 1.0f / a.k_scale;  // computed once, in fp32: the quantisation rule's 1 / scale
   a.v_inv = 1.0f / a.v_scale;
+}
+
+// Broadcast residual: g.residual holds `res_rows` rows (row stride g.ldr) under g.M output rows of n_out columns.
+// Sets GemmArgs::res_rows when a tile kernel takes the problem (use_v2 then finds a config, and every config
+// gemm2_cfg_supported accepts implements the wrap); otherwise the residual is expanded to M rows here and the problem
+// runs as an ordinary one.  Returns the expanded copy (the caller keeps it alive over the launch) or an undefined tensor.
+Tensor resolve_res_rows(shai::GemmArgs& g, int64_t res_rows, long n_out, const Tensor& like, long a_bytes, long w_bytes,
+                        long a2_bytes) {
+  SHAI_CHECK(res_rows > 0 && g.residual != nullptr && g.batch <= 1 && g.M % res_rows == 0,
+             "residual_rows must divide the row count of a 2D problem with a residual");
+  if (res_rows == g.M) return Tensor();
+  g.res_rows = (int)res_rows;
+  if (use_v2(g, a_bytes, w_bytes, a2_bytes)) return Tensor();
+  g.res_rows = 0;
+  Tensor r = at::from_blob(const_cast<shai::bf16_t*>(g.residual), {(long)res_rows, n_out}, {g.ldr, 1L},
+                           like.options().dtype(at::kBFloat16))
+                 .repeat({g.M / res_rows, 1});
+  g.residual = reinterpret_cast<const shai::bf16_t*>(r.data_ptr());
+  g.ldr = n_out;
+  return r;
+}
+
+// bias2d: contiguous, or a strided 2-D view (a column slice of a wider matrix, read in place through
+// GemmArgs::bias2d_ld) whose rows start 16-byte aligned (check_bf16 covers the base and the unit column stride)
+long bias2d_row_stride(const Tensor& t, long n) {
+  if (t.is_contiguous()) return n;
+  SHAI_CHECK(t.dim() == 2 && t.stride(0) >= n && t.stride(0) % 8 == 0,
+             "bias2d: contiguous, or a 2-D view with a row stride that is a multiple of 8 elements");
+  return t.stride(0);
 }
 
 void check_rows(const Tensor& t, const char* name) {
@@ -968,8 +1003,11 @@ void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tens
           double res_alpha, int64_t act, bool glu, const optional<Tensor>& gate, int64_t rows_per_gate,
           int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale, const optional<Tensor>& ln_mr,
           const optional<Tensor>& ln_s, const optional<Tensor>& gn_part, const optional<Tensor>& ln_stats,
-          double ln_eps, int64_t w_slice_rows) {
+          double ln_eps, int64_t w_slice_rows, int64_t res_rows) {
   check_rows(a, "a");
+  SHAI_CHECK(res_rows == 0 || (residual.has_value() && a.dim() == 2 && !w_scale.has_value() &&
+                               w.scalar_type() != at::ScalarType::Float4_e2m1fn_x2),
+             "residual_rows: 2D bf16-weight GEMMs with a residual");
   if (w.scalar_type() == at::ScalarType::Float4_e2m1fn_x2) {
     SHAI_CHECK(!bias2d && !gate && !ln_mr && !ln_s && !gn_part && !ln_stats && w_slice_rows == 0,
                "mxfp4 gemm: bias / activation / GLU / residual / folded RMSNorm epilogues only");
@@ -1022,13 +1060,15 @@ void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tens
   }
   if (bias2d) {
     check_bf16(*bias2d, "bias2d");
-    SHAI_CHECK(bias2d->is_contiguous() && bias2d->size(-1) == g.N && rows_per_bias2d > 0, "bias2d shape");
+    SHAI_CHECK(bias2d->size(-1) == g.N && rows_per_bias2d > 0, "bias2d shape");
     g.bias2d = cptr(*bias2d);
+    g.bias2d_ld = bias2d_row_stride(*bias2d, g.N);
     g.rows_per_bias2d = rows_per_bias2d;
   }
   if (residual) {
     check_bf16(*residual, "residual");
-    SHAI_CHECK(residual->size(-2) == g.M && residual->size(-1) == c.size(-1), "residual shape");
+    SHAI_CHECK(residual->size(-2) == (res_rows > 0 ? res_rows : g.M) && residual->size(-1) == c.size(-1),
+               "residual shape");
     g.residual = cptr(*residual);
     g.ldr = residual->stride(-2);
     g.batch_r = batched ? residual->stride(0) : 0;
@@ -1063,6 +1103,8 @@ void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tens
     return;
   }
   const long a_bytes = (batched ? (long)a.size(0) * a.stride(0) : (long)g.M * g.lda) * 2;
+  Tensor res_full;  // the expanded residual where no kernel takes the broadcast one
+  if (res_rows > 0) res_full = resolve_res_rows(g, res_rows, c.size(-1), a, a_bytes, (long)g.N * g.ldw * 2, 0);
   // tests / tools bypass the tuner: force_cfg = gemm2 config, 1000 = skinny kernel (heuristic K groups),
   // 1000 + kg = skinny kernel with kg K groups (separate fold), 1100 + kg = the same with the in-kernel fixup
   // 1200 + kg = the wide skinny kernel (gemv2.hip) with kg K groups (in-kernel fixup), 1250 + kg its 6-stage form
@@ -1155,7 +1197,7 @@ void conv2d(const Tensor& x, const optional<Tensor>& x2, const Tensor& w, const 
             const optional<Tensor>& in_scale, const optional<Tensor>& in_shift, int64_t in_act, int64_t kh,
             int64_t kw, int64_t stride, int64_t pad, bool upsample, int64_t act, double res_alpha,
             const optional<Tensor>& ln_mr, const optional<Tensor>& ln_s, const optional<Tensor>& gn_part,
-            const optional<Tensor>& ln_stats, double ln_eps, bool up_phases) {
+            const optional<Tensor>& ln_stats, double ln_eps, bool up_phases, int64_t res_rows) {
   check_bf16(x, "x");
   check_bf16(w, "w");
   check_bf16(out, "out");
@@ -1225,15 +1267,22 @@ void conv2d(const Tensor& x, const optional<Tensor>& x2, const Tensor& w, const 
   }
   if (bias2d) {
     check_bf16(*bias2d, "bias2d");
-    SHAI_CHECK(bias2d->is_contiguous() && bias2d->size(0) == g.Nimg && bias2d->size(-1) == g.N, "bias2d [N, Cout]");
+    SHAI_CHECK(bias2d->size(0) == g.Nimg && bias2d->size(-1) == g.N, "bias2d [N, Cout]");
     g.bias2d = cptr(*bias2d);
+    g.bias2d_ld = bias2d_row_stride(*bias2d, g.N);
     g.rows_per_bias2d = g.OH * g.OW;
   }
   if (residual) {
     check_bf16(*residual, "residual");
-    SHAI_CHECK(residual->is_contiguous() && residual->numel() == (long)g.M * g.N, "residual shape");
+    SHAI_CHECK(residual->is_contiguous() && residual->numel() == (long)(res_rows > 0 ? res_rows : g.M) * g.N,
+               "residual shape");
     g.residual = cptr(*residual);
     g.ldr = g.N;
+    // broadcast residual: set for the kernel checks below (the halo conv refuses it), settled before run_gemm
+    SHAI_CHECK(res_rows == 0 || g.M % res_rows == 0, "residual_rows must divide the output rows");
+    if (res_rows > 0 && res_rows != g.M) g.res_rows = (int)res_rows;
+  } else {
+    SHAI_CHECK(res_rows == 0, "residual_rows without a residual");
   }
   if (in_scale) {
     SHAI_CHECK(in_shift.has_value(), "in_scale requires in_shift");
@@ -1281,15 +1330,18 @@ void conv2d(const Tensor& x, const optional<Tensor>& x2, const Tensor& w, const 
     g.Cin1 = g.Cin;
     g.in_scale = g.in_shift = nullptr;
   }
-  run_gemm(g, x, xn.defined() ? xn.numel() * 2 : (xcat.defined() ? xcat.numel() * 2 : x.numel() * 2),
-           w.numel() * 2, (g.A2 != nullptr) ? x2->numel() * 2 : 0, &st);
+  const long a_bytes = xn.defined() ? xn.numel() * 2 : (xcat.defined() ? xcat.numel() * 2 : x.numel() * 2);
+  const long a2_bytes = (g.A2 != nullptr) ? x2->numel() * 2 : 0;
+  Tensor res_full;  // the expanded residual where no kernel takes the broadcast one
+  if (g.res_rows > 0) res_full = resolve_res_rows(g, g.res_rows, g.N, x, a_bytes, w.numel() * 2, a2_bytes);
+  run_gemm(g, x, a_bytes, w.numel() * 2, a2_bytes, &st);
 }
 
 // ---------------------------------------------------------------- attention
 void flash_attn(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor& o, double scale, bool causal,
                 int64_t causal_offset, const optional<Tensor>& kv_lens, const optional<Tensor>& q_lens,
                 const optional<Tensor>& bias, const optional<Tensor>& block_table, double k_scale,
-                double v_scale) {
+                double v_scale, int64_t q_batch_mod) {
   check_rows(q, "q");
   // fp8 (e4m3fn) k / v: the paged KV cache read directly (kv8_cache's layout checks stand in for check_rows)
   const bool f8 = kv8_cache(k, v, k_scale, v_scale);
@@ -1306,7 +1358,16 @@ void flash_attn(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor&
   a.kv_fp8 = f8;
   a.k_scale = (float)k_scale;
   a.v_scale = (float)v_scale;
-  a.B = q.size(0);
+  // shared queries: q holds q_batch_mod batches, o (and k / v) the full batch
+  SHAI_CHECK(q_batch_mod >= 0 && (q_batch_mod == 0 || (q.size(0) == q_batch_mod && o.size(0) % q_batch_mod == 0)),
+             "q_batch_mod: q must hold q_batch_mod batches and divide the output batch");
+  a.B = q_batch_mod > 0 ? o.size(0) : q.size(0);
+  if (q_batch_mod > 0) {  // the kernels index k / v / o by the output batch: their batches must be that large
+    SHAI_CHECK(!block_table.has_value() && (k.size(0) == a.B || k.size(0) == 1) && (v.size(0) == a.B || v.size(0) == 1),
+               "q_batch_mod: k / v must hold the output's batch (or 1), unpaged");
+    SHAI_CHECK(o.size(1) == q.size(1) && o.size(2) == q.size(2) && o.size(3) == q.size(3),
+               "q_batch_mod: o must be [B, Sq, Hq, D] of q's trailing dims");
+  }
   a.Sq = q.size(1);
   a.Hq = q.size(2);
   a.D = q.size(3);
@@ -1360,12 +1421,24 @@ void flash_attn(const Tensor& q, const Tensor& k, const Tensor& v, const Tensor&
     SHAI_CHECK(bias->is_contiguous() && bias->numel() == (long)a.Hq * a.Sq * a.Skv, "bias must be [Hq, Sq, Skv]");
     a.bias = cptr(*bias);
   }
+  Tensor q_full;  // the expanded queries where the routed kernel reads q per batch
+  if (q_batch_mod > 0 && q_batch_mod != a.B) {
+    a.q_batch_mod = (int)q_batch_mod;
+    if (!shai::flash_q_mod_supported(a)) {
+      q_full = q.repeat({a.B / q_batch_mod, 1, 1, 1});
+      a.q_batch_mod = 0;
+      a.q = cptr(q_full);
+      a.q_bs = q_full.stride(0);
+      a.q_ts = q_full.stride(1);
+    }
+  }
   if (a.D == 512) {
     SHAI_CHECK(shai::attn512_supported(a), "D = 512 attention: one head, no mask / bias / causal / paged K/V, "
                                            "8-element aligned strides");
     shai::launch_attn512(a, stream());
     return;
   }
+  SHAI_CHECK(a.q_batch_mod == 0 || shai::flash_q_mod_supported(a), "q_batch_mod reached a kernel without it");
   shai::launch_flash_attn(a, stream());
 }
 
@@ -1836,7 +1909,7 @@ void dequant_mxfp4(const Tensor& wq, const Tensor& scales, const Tensor& out) {
 // when the problem is outside the kernel's contract; the caller then runs the GEMM and the norm separately.
 bool gemm_lnout(const Tensor& a, const Tensor& w, const Tensor& c, const Tensor& c2, const optional<Tensor>& bias,
                 const Tensor& residual, double res_alpha, const optional<Tensor>& gamma, const optional<Tensor>& beta,
-                double eps) {
+                double eps, int64_t res_rows) {
   check_rows(a, "a");
   check_rows(w, "w");
   check_bf16(c, "c");
@@ -1851,8 +1924,10 @@ bool gemm_lnout(const Tensor& a, const Tensor& w, const Tensor& c, const Tensor&
   g.K = a.size(1);
   g.N = w.size(0);
   SHAI_CHECK(w.size(1) == g.K, "gemm_lnout K mismatch");
-  SHAI_CHECK(c.size(0) == g.M && c.size(1) == g.N && c2.sizes() == c.sizes() && residual.sizes() == c.sizes(),
+  SHAI_CHECK(c.size(0) == g.M && c.size(1) == g.N && c2.sizes() == c.sizes() && residual.size(1) == g.N &&
+                 residual.size(0) == (res_rows > 0 ? res_rows : g.M),
              "gemm_lnout output / residual shape mismatch");
+  if (res_rows > 0 && res_rows != g.M) g.res_rows = (int)res_rows;  // broadcast residual: gemm_ws_supported decides
   if (c.stride(0) != c2.stride(0)) return false;
   g.lda = a.stride(0);
   g.ldw = w.stride(0);
@@ -1951,13 +2026,13 @@ TORCH_LIBRARY(shai, m) {
   m.def("groupnorm_from_partials(Tensor part1, Tensor? part2, int C1, int C2, int Nimg, int HW, Tensor? gamma, Tensor? beta, Tensor(a!) scale, Tensor(b!) shift, int G, float eps) -> ()");
   m.def("col_partials(Tensor x, Tensor(a!) part) -> ()");
   m.def("row_moments(Tensor x, Tensor(a!) mr, float eps) -> ()");
-  m.def("gemm(Tensor a, Tensor w, Tensor(a!) c, Tensor? bias, Tensor? bias2d, int rows_per_bias2d, Tensor? residual, float alpha, float res_alpha, int act, bool glu, Tensor? gate=None, int rows_per_gate=1, int force_cfg=-1, float rms_eps=-1.0, Tensor? w_scale=None, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, int w_slice_rows=0) -> ()");
+  m.def("gemm(Tensor a, Tensor w, Tensor(a!) c, Tensor? bias, Tensor? bias2d, int rows_per_bias2d, Tensor? residual, float alpha, float res_alpha, int act, bool glu, Tensor? gate=None, int rows_per_gate=1, int force_cfg=-1, float rms_eps=-1.0, Tensor? w_scale=None, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, int w_slice_rows=0, int res_rows=0) -> ()");
   m.def("dequant_fp8(Tensor w8, Tensor scale, Tensor(a!) out) -> ()");
   m.def("dequant_mxfp4(Tensor wq, Tensor scales, Tensor(a!) out) -> ()");
   m.def("layernorm_mod(Tensor x, Tensor scale, Tensor shift, Tensor(a!) out, int rows_per_mod, float eps) -> ()");
   m.def("qk_norm_rope(Tensor(a!) x, Tensor? q_w, Tensor? k_w, Tensor? cos, Tensor? sin, int H, int D, int S, float eps) -> ()");
-  m.def("conv2d(Tensor x, Tensor? x2, Tensor w, Tensor(a!) out, Tensor? bias, Tensor? bias2d, Tensor? residual, Tensor? in_scale, Tensor? in_shift, int in_act, int kh, int kw, int stride, int pad, bool upsample, int act, float res_alpha, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, bool up_phases=False) -> ()");
-  m.def("flash_attn(Tensor q, Tensor k, Tensor v, Tensor(a!) o, float scale, bool causal, int causal_offset, Tensor? kv_lens, Tensor? q_lens, Tensor? bias, Tensor? block_table, float k_scale=1.0, float v_scale=1.0) -> ()");
+  m.def("conv2d(Tensor x, Tensor? x2, Tensor w, Tensor(a!) out, Tensor? bias, Tensor? bias2d, Tensor? residual, Tensor? in_scale, Tensor? in_shift, int in_act, int kh, int kw, int stride, int pad, bool upsample, int act, float res_alpha, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, bool up_phases=False, int res_rows=0) -> ()");
+  m.def("flash_attn(Tensor q, Tensor k, Tensor v, Tensor(a!) o, float scale, bool causal, int causal_offset, Tensor? kv_lens, Tensor? q_lens, Tensor? bias, Tensor? block_table, float k_scale=1.0, float v_scale=1.0, int q_batch_mod=0) -> ()");
   m.def("paged_attn_varlen(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor kv_lens, Tensor q_lens, Tensor q_start, int max_q, float scale, bool causal, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor ctx_lens, Tensor(b!) ws, int num_splits, float scale, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("kv_write(Tensor k, Tensor v, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots, float k_scale=1.0, float v_scale=1.0) -> ()");
@@ -1977,7 +2052,7 @@ TORCH_LIBRARY(shai, m) {
         "Tensor ctx_lens, Tensor positions, Tensor cos, Tensor sin, Tensor slots, Tensor(d!) ws, int h, int hk, "
         "int num_splits, float scale, Tensor? qkv_ws=None, int qkv_kg=0, int qkv_k=0, float qkv_eps=-1.0, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("gemm_partials(Tensor a, Tensor w, float rms_eps) -> Tensor");
-  m.def("gemm_lnout(Tensor a, Tensor w, Tensor(a!) c, Tensor(b!) c2, Tensor? bias, Tensor residual, float res_alpha, Tensor? gamma, Tensor? beta, float eps) -> bool");
+  m.def("gemm_lnout(Tensor a, Tensor w, Tensor(a!) c, Tensor(b!) c2, Tensor? bias, Tensor residual, float res_alpha, Tensor? gamma, Tensor? beta, float eps, int res_rows=0) -> bool");
   m.def("gemm_tuning() -> str[]", &gemm_tuning);
   m.def("gemm_tuning_export() -> str[]", &gemm_tuning_export);
   m.def("gemm_tuning_import(str[] entries) -> int", &gemm_tuning_import);

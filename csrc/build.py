@@ -57,7 +57,8 @@ EXTRA_KFLAGS = {"kernels/attention3.hip": "-mllvm -amdgpu-mfma-vgpr-form -fno-sl
                 "kernels/gemm_w4.hip": "-mllvm -pragma-unroll-threshold=100000",
                 "kernels/gemm_ws.hip": "-mllvm -pragma-unroll-threshold=100000 -fno-slp-vectorize",
                 "kernels/conv_halo.hip": "-mllvm -pragma-unroll-threshold=100000 -fno-slp-vectorize"}
-BINDING_SRCS = ["bindings.cpp"]
+# test_probes.cpp: test-only operators (host probes of the *_supported checks)
+BINDING_SRCS = ["bindings.cpp", "test_probes.cpp"]
 RUNTIME_SRCS = ["runtime/block_manager.cpp", "runtime/scheduler.cpp"]
 COMM_SRCS = ["comm/p2p_allreduce.hip"]
 

@@ -266,20 +266,26 @@ __global__ void __launch_bounds__(256, 2) flash64_kernel(const AttnArgs p) {
   }
 }
 
+static bool flash64_dma_on() {  // SHAI_FLASH64_DMA=0: the register-staged flash64_kernel (A/B)
+  static const bool dma = [] {
+    const char* e = getenv("SHAI_FLASH64_DMA");
+    return e == nullptr || atoi(e) != 0;
+  }();
+  return dma;
+}
+
 bool flash64_supported(const AttnArgs& a) {
   static const bool on = [] {
     const char* e = getenv("SHAI_FLASH64");
     return e == nullptr || atoi(e) != 0;
   }();
+  // shared queries (q_batch_mod): the LDS-DMA kernels only; the register-staged kernel below reads q per batch
+  if (a.q_batch_mod != 0 && !(flash64_dma_on() && flash64_dma_supported(a))) return false;
   return on && a.D == 64 && a.bias == nullptr && a.block_table == nullptr && ((a.k_ts | a.v_ts | a.q_ts) & 7) == 0;
 }
 
 void launch_flash64(const AttnArgs& a, hipStream_t s) {
-  static const bool dma = [] {  // SHAI_FLASH64_DMA=0: the register-staged kernel below (A/B)
-    const char* e = getenv("SHAI_FLASH64_DMA");
-    return e == nullptr || atoi(e) != 0;
-  }();
-  if (dma && flash64_dma_supported(a)) {
+  if (flash64_dma_on() && flash64_dma_supported(a)) {
     // two 32-query groups per wave when the 256-query grid still fills the chip several times over
     // (short key ranges -- SD2.1 cross-attention over 77 text tokens -- stay on the 128-query kernel: 123 vs 142 us)
     if ((long)((a.Sq + 255) / 256) * a.Hq * a.B >= 1024 && a.Skv >= 512) launch_flash64_x2(a, s);
@@ -308,6 +314,13 @@ int set_flash128x2(int mode) {
   const int prev = flash128x2_mode();
   if (mode >= 0) g_f128x2 = mode;
   return prev;
+}
+
+// shared queries run only where the routing below ends in flash64_dma / flash64x2: a caller checks this before
+// launch_flash_attn and expands q otherwise (bindings.cpp raises if the two ever disagree)
+bool flash_q_mod_supported(const AttnArgs& a) {
+  return a.q_batch_mod > 0 && !a.kv_fp8 && getenv("SHAI_FLASH_V1") == nullptr && flash64_supported(a) &&
+         a.B % a.q_batch_mod == 0;
 }
 
 void launch_flash_attn(const AttnArgs& a, hipStream_t s) {

@@ -579,7 +579,7 @@ __global__ void __launch_bounds__(512) flash2_kernel(const AttnArgs p) {
 }
 
 bool flash2_supported(const AttnArgs& a) {
-  if (a.bias != nullptr || a.block_table != nullptr) return false;
+  if (a.bias != nullptr || a.block_table != nullptr || a.q_batch_mod != 0) return false;
   if (a.D != 64 && a.D != 128) return false;
   if (a.Sq < 512) return false;  // 256-query workgroups; v1's 128-query blocks waste less on short rows
   if (a.Skv < 512) return false;  // a few key tiles: v1 has less per-workgroup setup (cross-attention to 77 tokens)

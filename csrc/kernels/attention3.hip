@@ -84,7 +84,8 @@ __global__ void __launch_bounds__(256, OCC) flash64_dma_kernel(const AttnArgs p)
 
   f3bf16x8 qf[NS];
   {
-    const bf16_t* qp = p.q + (p.q_start ? (long)p.q_start[b] * p.q_ts : (long)b * p.q_bs) +
+    const int bq = p.q_batch_mod > 0 ? b % p.q_batch_mod : b;  // shared queries: q holds q_batch_mod batches
+    const bf16_t* qp = p.q + (p.q_start ? (long)p.q_start[b] * p.q_ts : (long)bq * p.q_bs) +
                         (long)min(qi, q_len - 1) * p.q_ts + (long)hq * D;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -301,9 +302,10 @@ __global__ void __launch_bounds__(256, 2) flash64x2_kernel(const AttnArgs p) {
   if (ntiles > 0) dma(0, 0);
 
   f3bf16x8 qf[G][NS];
+  const int bq = p.q_batch_mod > 0 ? b % p.q_batch_mod : b;  // shared queries: q holds q_batch_mod batches
 #pragma unroll
   for (int g = 0; g < G; ++g) {
-    const bf16_t* qp = p.q + (p.q_start ? (long)p.q_start[b] * p.q_ts : (long)b * p.q_bs) +
+    const bf16_t* qp = p.q + (p.q_start ? (long)p.q_start[b] * p.q_ts : (long)bq * p.q_bs) +
                         (long)min(qi[g], q_len - 1) * p.q_ts + (long)hq * D;
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
@@ -767,6 +769,7 @@ __global__ void __launch_bounds__(256, 1) flash128x2_kernel(const AttnArgs p) {
 // D = 128, no additive bias / paged K/V, 16-B aligned rows; causal (+ offset), per-batch q / kv lengths, packed
 // varlen q / o and GQA as flash2
 bool flash128x2_supported(const AttnArgs& a) {
+  if (a.q_batch_mod != 0) return false;
   return a.D == 128 && a.bias == nullptr && a.block_table == nullptr && ((a.k_ts | a.v_ts | a.q_ts) & 7) == 0 &&
          (long)a.Skv * a.k_ts * 2 < 0x7fffffffL && (long)a.Skv * a.v_ts * 2 < 0x7fffffffL;
 }
@@ -779,8 +782,10 @@ void launch_flash128x2(const AttnArgs& a, hipStream_t s) {
 }
 
 // Same contract as flash64 (attention.hip): D = 64, causal (+ offset), per-batch q / kv lengths, packed varlen
-// q / o, GQA; K / V rows addressed through 32-bit buffer offsets.
+// q / o, GQA; K / V rows addressed through 32-bit buffer offsets.  Shared queries (q_batch_mod: flash64_dma and
+// flash64x2 read batch b's Q rows from batch b % q_batch_mod) not together with packed varlen q.
 bool flash64_dma_supported(const AttnArgs& a) {
+  if (a.q_batch_mod < 0 || (a.q_batch_mod > 0 && a.q_start != nullptr)) return false;
   return a.D == 64 && a.bias == nullptr && a.block_table == nullptr && ((a.k_ts | a.v_ts | a.q_ts) & 7) == 0 &&
          (long)a.Skv * a.k_ts * 2 < 0x7fffffffL && (long)a.Skv * a.v_ts * 2 < 0x7fffffffL;
 }
@@ -965,6 +970,7 @@ __global__ void __launch_bounds__(512, 1) attn512_kernel(const AttnArgs p) {
 }
 
 bool attn512_supported(const AttnArgs& a) {
+  if (a.q_batch_mod != 0) return false;
   return a.D == 512 && a.Hq == 1 && a.Hkv == 1 && a.Sq == a.Skv && a.bias == nullptr && a.block_table == nullptr &&
          !a.causal && a.kv_lens == nullptr && a.q_lens == nullptr && a.q_start == nullptr &&
          ((a.k_ts | a.v_ts | a.q_ts | a.o_ts) & 7) == 0 && (long)a.Skv * a.k_ts * 2 < 0x7fffffffL &&

@@ -391,7 +391,7 @@ __global__ void __launch_bounds__(64 * WAVES, 1) conv_halo_kernel(const GemmArgs
       bj[j][2] = bf2f(bb[1] & 0xffff); bj[j][3] = bf2f(bb[1] >> 16);
     }
     if (p.bias2d) {  // the tile lies in one image: one time-embedding row
-      const uint2_ bb = *reinterpret_cast<const uint2_*>(p.bias2d + (long)img * p.N + n);
+      const uint2_ bb = *reinterpret_cast<const uint2_*>(p.bias2d + (long)img * bias2d_stride(p) + n);
       bj[j][0] += bf2f(bb[0] & 0xffff); bj[j][1] += bf2f(bb[0] >> 16);
       bj[j][2] += bf2f(bb[1] & 0xffff); bj[j][3] += bf2f(bb[1] >> 16);
     }
@@ -480,6 +480,7 @@ static int hc_bn(const GemmArgs& a) { return a.N % 160 == 0 ? 160 : (a.N % 128 =
 
 bool conv_halo_supported(const GemmArgs& a) {
   if (!a.conv || a.KH != 3 || a.KW != 3 || a.stride != 1 || a.pad != 1 || a.batch > 1) return false;
+  if (a.res_rows != 0) return false;  // no broadcast residual
   if (a.OW != 16 && a.OW != 32 && a.OW != 64) return false;
   const int TR = HC_BM / a.OW;
   if (a.OH % TR != 0 || (TR + 2) * (a.OW + 2) > HC_HPIX_MAX) return false;
@@ -499,7 +500,7 @@ bool conv_halo_supported(const GemmArgs& a) {
   if (!hc_al16(a.A) || !hc_al16(a.W) || !hc_al16(a.C) || (a.A2 && !hc_al16(a.A2)) ||
       (a.residual && !hc_al16(a.residual)) || (a.bias && !hc_al16(a.bias)) || (a.bias2d && !hc_al16(a.bias2d)))
     return false;
-  if (a.bias2d && a.rows_per_bias2d != a.OH * a.OW) return false;
+  if (a.bias2d && (a.rows_per_bias2d != a.OH * a.OW || bias2d_stride(a) % 8 != 0)) return false;
   const long src_pix = (long)a.Nimg * a.H * a.Wd;
   const int cs_a = a.A2 ? a.Cin1 : a.Cin;
   if (src_pix * cs_a * 2 >= 0x7fffffffL || (a.A2 && src_pix * (a.Cin - a.Cin1) * 2 >= 0x7fffffffL)) return false;

@@ -218,7 +218,7 @@ __global__ void __launch_bounds__(256, 2) gemm_kernel(const GemmArgs p) {
   for (int i = 0; i < 2; ++i) {
     const int m = m0 + wm * 64 + i * 32 + fr;
     if (m >= p.M) continue;
-    const bf16_t* b2 = p.bias2d ? p.bias2d + (long)(m / p.rows_per_bias2d) * p.N : nullptr;
+    const bf16_t* b2 = p.bias2d ? p.bias2d + (long)(m / p.rows_per_bias2d) * bias2d_stride(p) : nullptr;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
 #pragma unroll

@@ -492,6 +492,12 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
       } else {
         bf16_t* __restrict__ C = p.C + (long)b * p.batch_c;
         const bf16_t* __restrict__ R = p.residual ? p.residual + (long)b * p.batch_r : nullptr;
+        if (p.res_rows > 0) {
+          // broadcast residual (host: res_rows % 256 == 0 divides M, batch 1): the tile's rows m0 .. m0 + 255 wrap as a
+          // whole, so the tile's residual base moves once and every R + m * ldr below reads row m % res_rows
+          SHAI_DASSERT(p.res_rows % G4_BM == 0 && p.M % p.res_rows == 0 && b == 0);
+          R -= (long)(m0 - m0 % p.res_rows) * p.ldr;
+        }
         // output row of GEMM row m: itself, or (phase conv) its pixel on the upsampled grid -- shifts and masks only
         // (up2_row): a division per row bloats the unrolled epilogue until the accumulators leave registers
         const auto orow = [&](int m) -> long {
@@ -529,7 +535,8 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
         }
         // per-image bias (time embedding) in the wide path: each wave's 128 rows lie inside one image
         const bool b2ok = p.bias2d == nullptr ||
-                          (WIDE && (p.rows_per_bias2d & 127) == 0 && (p.N & 7) == 0 && ((uintptr_t)p.bias2d & 15) == 0);
+                          (WIDE && (p.rows_per_bias2d & 127) == 0 && ((p.N | bias2d_stride(p)) & 7) == 0 &&
+                           ((uintptr_t)p.bias2d & 15) == 0);  // 16-byte loads from the (strided) row
         const bool fast = m0 + G4_BM <= p.M && n0 + BN <= p.N && b2ok && p.gate == nullptr &&
                           (p.ldc & 3) == 0 && (R == nullptr || (p.ldr & 3) == 0);
         if constexpr (WIDE) {
@@ -556,7 +563,7 @@ __global__ void __launch_bounds__(512) gemm4_kernel(const GemmArgs p, float* __r
               bt[2] = bf2f(bb[1] & 0xffff); bt[3] = bf2f(bb[1] >> 16);
             }
             if (p.bias2d != nullptr) {  // b2ok: the wave's 128 rows share one bias2d row
-              const bf16_t* b2 = p.bias2d + (long)((m0 + wm * 128) / p.rows_per_bias2d) * p.N;
+              const bf16_t* b2 = p.bias2d + (long)((m0 + wm * 128) / p.rows_per_bias2d) * bias2d_stride(p);
 #pragma unroll
               for (int q = 0; q < NP; ++q) {
                 float t8[8];
@@ -866,6 +873,9 @@ bool gemm4_supported(const GemmArgs& a) {
   // weight slices: whole 256-row tiles per slice, plain batch-1 GEMM
   if (a.w_slice_rows != 0 && (a.w_slice_rows % G4_BM != 0 || a.conv || a.batch > 1 || a.M % a.w_slice_rows != 0))
     return false;
+  // broadcast residual: whole 256-row tiles per wrap (the epilogue moves the tile's residual base, the split-K fold
+  // wraps per row)
+  if (a.res_rows != 0 && !res_rows_ok(a, G4_BM)) return false;
   if (a.conv) {
     if (a.Cin % 64 != 0) return false;
     // tap positions are held packed in 16 bits each (g4_conv_off)
@@ -890,7 +900,7 @@ bool gemm4_stats_ok(const GemmArgs& a, int bn) {
   if (a.M % G4_BM != 0 || a.N % bn != 0 || a.ldc % 8 != 0 || !al16(a.C)) return false;
   if (a.residual != nullptr && (a.ldr % 8 != 0 || !al16(a.residual))) return false;
   if (a.bias != nullptr && !al16(a.bias)) return false;
-  if (a.bias2d != nullptr && (a.rows_per_bias2d % 128 != 0 || a.N % 8 != 0 || !al16(a.bias2d))) return false;
+  if (a.bias2d != nullptr && (a.rows_per_bias2d % 128 != 0 || a.N % 8 != 0 || bias2d_stride(a) % 8 != 0 || !al16(a.bias2d))) return false;
   // phase conv over image groups (H W < 256): the GEMM's 128-row blocks interleave the group's images, and the partials'
   // consumer maps block b to image b * 128 / (OH OW) -- statistics from a pass over the output instead
   if (a.upsample == 2 && a.H * a.Wd < G4_BM) return false;

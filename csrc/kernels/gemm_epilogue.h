@@ -46,8 +46,8 @@ __device__ __forceinline__ void epilogue4(const GemmArgs& p, bf16_t* C, const bf
     }
   }
   if (p.bias2d) {
-    const bf16_t* b2 = p.bias2d + (long)(m / p.rows_per_bias2d) * p.N;
-    if (full && (p.N & 3) == 0) {
+    const bf16_t* b2 = p.bias2d + (long)(m / p.rows_per_bias2d) * bias2d_stride(p);
+    if (full && ((p.N | bias2d_stride(p)) & 3) == 0) {
       const uint2_ bb = *reinterpret_cast<const uint2_*>(b2 + n);
       v[0] += bf2f(bb[0] & 0xffff); v[1] += bf2f(bb[0] >> 16);
       v[2] += bf2f(bb[1] & 0xffff); v[3] += bf2f(bb[1] >> 16);

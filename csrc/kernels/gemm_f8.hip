@@ -233,6 +233,7 @@ __global__ void __launch_bounds__(256) quant_rows_fp8_kernel(const bf16_t* __res
 }
 
 bool gemm_f8_supported(const GemmArgs& a) {
+  if (a.res_rows != 0) return false;  // no broadcast residual
   return a.M >= 1 && a.N >= 1 && a.K % 16 == 0 && a.lda % 16 == 0 && a.ldw % 16 == 0 && !a.conv && a.batch <= 1 &&
          a.bias2d == nullptr && a.gate == nullptr && (!a.glu || a.N % 4 == 0) && (long)a.M * a.lda < 0x7fffffffL &&
          (long)a.N * a.ldw < 0x7fffffffL;

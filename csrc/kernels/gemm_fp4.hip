@@ -261,6 +261,7 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_fp4_kernel(const GemmArgs p
 // bias, activation, GLU (SILU / GELU / GELU_TANH), residual, alpha, row strides.  A folded RMSNorm (a.rms) is not
 // taken: the caller runs the unweighted row-norm pass first, as the bf16 tile kernels have it.
 bool gemm_fp4_supported(const GemmArgs& a) {
+  if (a.res_rows != 0) return false;  // no broadcast residual
   return a.w_mx_scale != nullptr && a.w_scale == nullptr && !a.conv && a.batch <= 1 && a.w_slice_rows == 0 &&
          a.M > 64 && a.K >= 32 && a.K % 32 == 0 && a.N >= 1 && a.N % 2 == 0 && (!a.glu || a.N % 4 == 0) &&
          tile_act_supported(a) && !a.rms && a.bias2d == nullptr && a.gate == nullptr && a.in_scale == nullptr &&

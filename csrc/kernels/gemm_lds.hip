@@ -439,7 +439,9 @@ __global__ void gemm_splitk_reduce(const GemmArgs p, const float* __restrict__ w
     }
     // phase conv: row m's output pixel (no residual on that path)
     bf16_t* C = p.upsample == 2 ? p.C + (up2_out_row(p, m) - m) * p.ldc : p.C;
-    epilogue4<GLU, ACT>(p, C, p.residual, m, n, v);
+    // broadcast residual (v4 split-K only): epilogue4 reads R + m * ldr, so the base moves back by the wraps before m
+    const bf16_t* R = p.res_rows > 0 ? p.residual - (long)(m - m % p.res_rows) * p.ldr : p.residual;
+    epilogue4<GLU, ACT>(p, C, R, m, n, v);
   }
 }
 
@@ -675,6 +677,9 @@ bool gemm2_cfg_supported(const GemmArgs& a, int cfg) {
   // and tiles to weight slices
   if (a.upsample == 2 || a.w_slice_rows != 0) return cfg >= kV4Cfg && cfg < kV4Cfg + 4 && gemm4_supported(a);
   // folded LayerNorm (row_mr): only the v4 kernel's epilogue applies it, and only unsplit, batch 1
+  // broadcast residual (res_rows): the v4 epilogue / split-K fold and the W-stationary kernel wrap the tile's residual
+  // base; the v2 tiles and the four-wave kernel would read the residual past its end
+  if (a.res_rows != 0 && !(cfg == kWsCfg || (cfg >= kV4Cfg && cfg < kV4Cfg + 4))) return false;
   if (a.row_mr != nullptr)
     return cfg == kWsCfg ? gemm_ws_supported(a) : cfg >= kV4Cfg && cfg < kV4Cfg + 4 && a.batch <= 1 && gemm4_supported(a);
   if (cfg == kWsCfg) return gemm_ws_supported(a);

@@ -305,7 +305,8 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(const GemmArgs p) {
   const bf16_t* R = p.residual ? p.residual + (long)b * p.batch_r : nullptr;
   const uintptr_t ptrs = (uintptr_t)C | (uintptr_t)R | (uintptr_t)p.bias | (uintptr_t)p.bias2d | (uintptr_t)p.gate;
   const bool full = m0 + BM <= p.M && n0 + BN <= p.N && ((p.ldc | (R ? p.ldr : 0)) & 7) == 0 && (ptrs & 15) == 0 &&
-                    (p.bias2d == nullptr || (p.N & 7) == 0) && (p.gate == nullptr || (p.gate_stride & 7) == 0);
+                    (p.bias2d == nullptr || ((p.N | bias2d_stride(p)) & 7) == 0) &&
+                    (p.gate == nullptr || (p.gate_stride & 7) == 0);
   constexpr int NQ = BNB / 2;
   if (full) {
     float bq[NQ][8];
@@ -319,7 +320,7 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(const GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < BMB; ++i) {
       const int m = m0 + wr * WM + 16 * i + fr;
-      const bf16_t* b2 = p.bias2d ? p.bias2d + (long)(m / p.rows_per_bias2d) * p.N : nullptr;
+      const bf16_t* b2 = p.bias2d ? p.bias2d + (long)(m / p.rows_per_bias2d) * bias2d_stride(p) : nullptr;
       const bf16_t* gr = p.gate ? p.gate + ((long)b * p.M + m) / p.rows_per_gate * p.gate_stride : nullptr;
 #pragma unroll
       for (int q = 0; q < NQ; ++q) {
@@ -383,7 +384,7 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(const GemmArgs p) {
       for (int jb = 0; jb < BNB; ++jb) {
         const int n = n0 + wc * WN + (jb >> 1) * 32 + 8 * fq + 4 * (jb & 1);
         if (m >= p.M) continue;
-        const bf16_t* b2 = p.bias2d ? p.bias2d + (long)(m / p.rows_per_bias2d) * p.N : nullptr;
+        const bf16_t* b2 = p.bias2d ? p.bias2d + (long)(m / p.rows_per_bias2d) * bias2d_stride(p) : nullptr;
         const bf16_t* gr = p.gate ? p.gate + ((long)b * p.M + m) / p.rows_per_gate * p.gate_stride : nullptr;
 #pragma unroll
         for (int e = 0; e < 4; e += (GLU ? 2 : 1)) {
@@ -409,6 +410,7 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(const GemmArgs p) {
 
 bool gemm_w4_supported(const GemmArgs& a) {
   if (a.in_scale != nullptr || a.rms || quantized_w(a) || (a.glu && a.N % 8 != 0)) return false;
+  if (a.res_rows != 0) return false;  // no broadcast residual
   if (a.K % 8 != 0 || a.lda % 8 != 0 || a.ldw % 8 != 0) return false;  // 16-B source chunks
   if ((long)a.N * a.ldw * 2 >= 0x7fffffffL) return false;
   if (a.conv) {

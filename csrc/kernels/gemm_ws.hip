@@ -171,7 +171,7 @@ __global__ void __launch_bounds__(256, 1) gemm_ws_kernel(const GemmArgs p, int s
   uint32_t roff[T::R_DMA > 0 ? T::R_DMA : 1];
   int rrow[T::R_DMA > 0 ? T::R_DMA : 1];
   if constexpr (RES) {
-    rR = ws_rsrc(p.residual, (long)p.M * p.ldr * 2);
+    rR = ws_rsrc(p.residual, (long)(p.res_rows > 0 ? p.res_rows : p.M) * p.ldr * 2);
     // residual instruction q of this wave covers image bytes [1024 (wid * R_DMA + q), + 1024): lane -> (row, chunk)
 #pragma unroll
     for (int q = 0; q < T::R_DMA; ++q) {
@@ -204,10 +204,14 @@ __global__ void __launch_bounds__(256, 1) gemm_ws_kernel(const GemmArgs p, int s
                                                  off, 0, 0, 0);
       }
     if constexpr (RES) {
+      // broadcast residual (res_rows: a multiple of BM that divides M, gemm_ws_supported): the tile's rows wrap as a
+      // whole, so only its base row changes
+      const int mr = p.res_rows > 0 ? m0 % p.res_rows : m0;
+      SHAI_DASSERT(p.res_rows == 0 || (p.res_rows % BM == 0 && p.M % p.res_rows == 0));
 #pragma unroll
       for (int q = 0; q < T::R_DMA; ++q) {
-        const uint32_t off = rrow[q] < rows ? (uint32_t)m0 * (uint32_t)(p.ldr * 2) + roff[q] : WS_OOB;
-        SHAI_DASSERT_DMA(off, (long)p.M * p.ldr * 2, WS_OOB);
+        const uint32_t off = rrow[q] < rows ? (uint32_t)mr * (uint32_t)(p.ldr * 2) + roff[q] : WS_OOB;
+        SHAI_DASSERT_DMA(off, (long)(p.res_rows > 0 ? p.res_rows : p.M) * p.ldr * 2, WS_OOB);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rR, (ws_lds_void*)(rs + 1024 * (wid * T::R_DMA + q)), 16, off, 0, 0,
                                                  0);
       }
@@ -615,6 +619,7 @@ bool gemm_ws_supported(const GemmArgs& a) {
   if (a.conv || a.batch > 1 || a.A2 || a.in_scale || a.rms || quantized_w(a) || a.gate || a.bias2d) return false;
   if (a.K != 320 || a.N % WS_BN != 0 || a.M <= 0) return false;
   if (a.glu && a.residual) return false;
+  if (a.res_rows != 0 && !res_rows_ok(a, 32)) return false;  // whole 32-row residual tiles (BM of every RES variant)
   if (a.lda % 8 || a.ldw % 8 || a.ldc % 8 || (a.residual && a.ldr % 8)) return false;
   const auto al = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   if (!al(a.A) || !al(a.W) || !al(a.C) || (a.residual && !al(a.residual))) return false;

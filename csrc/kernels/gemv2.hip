@@ -104,6 +104,7 @@ constexpr int S2_MB = 64;  // X rows (two 32-row groups)
 constexpr size_t s2_lds(int stages) { return (size_t)stages * WBf16::stage_bytes(S2_MB); }
 
 bool skinny2_supported(const GemmArgs& a) {
+  if (a.res_rows != 0) return false;  // no broadcast residual
   // (QUICK_GELU is not instantiated by launch_skinny2: such problems stay on the other kernels)
   return a.M >= 1 && a.M <= S2_MB && !a.conv && a.batch <= 1 && a.w_slice_rows == 0 && !quantized_w(a) &&
          a.bias2d == nullptr &&

@@ -163,6 +163,7 @@ void launch_dequant_mxfp4(const uint8_t* wq, const uint8_t* scales, bf16_t* out,
 // ---------------------------------------------------------------------------- host side
 // a.W: codes [N, K / 2] bytes at a row stride of a.ldw BYTES; a.w_mx_scale: [ceil(K / 128), N, 4] bytes
 bool skinny_fp4_supported(const GemmArgs& a) {
+  if (a.res_rows != 0) return false;  // no broadcast residual
   return a.w_mx_scale != nullptr && a.w_scale == nullptr && !a.conv && a.batch <= 1 && a.w_slice_rows == 0 &&
          a.M >= 1 && a.M <= 64 && a.K >= 32 && a.K % 32 == 0 && a.N >= 1 && a.N % 2 == 0 && (!a.glu || a.N % 4 == 0) &&
          a.bias2d == nullptr && a.gate == nullptr && a.in_scale == nullptr && a.row_mr == nullptr &&

@@ -149,7 +149,21 @@ struct GemmArgs {
   // > 0: rows [s w_slice_rows, (s + 1) w_slice_rows) multiply weight slice s (W is [M / w_slice_rows][N][ldw]; v4
   // kernel only, w_slice_rows % 256 == 0): a per-image weight, e.g. a GroupNorm's per-image scale folded into W
   int w_slice_rows;
+  // > 0: the residual holds res_rows rows and output row m adds residual row m % res_rows (a B-image stream under 2B
+  // output images: the classifier-free-guidance halves that share a prefix).  Batch 1; res_rows divides M and is a
+  // multiple of the kernel's row tile (256: v4 and its split-K fold; 32: W-stationary), so no tile straddles the wrap
+  // and the tile's residual base is (m0 % res_rows) * ldr.  Every other kernel rejects such a problem.  (Appended:
+  // the other fields keep their offsets in the kernels' arguments)
+  int res_rows;
+  // row stride of bias2d in elements; 0 = N (a contiguous [M / rows_per_bias2d, N] matrix).  A column slice of a wider
+  // matrix (the batched time-embedding GEMM's output) is read in place by every kernel that takes bias2d.  (Appended)
+  long bias2d_ld;
 };
+__host__ __device__ inline long bias2d_stride(const GemmArgs& a) { return a.bias2d_ld > 0 ? a.bias2d_ld : a.N; }
+// the broadcast residual's host contract for a kernel of `tile` output rows per tile
+inline bool res_rows_ok(const GemmArgs& a, int tile) {
+  return a.res_rows > 0 && a.residual != nullptr && a.batch <= 1 && a.res_rows % tile == 0 && a.M % a.res_rows == 0;
+}
 // (conv, GLU, activation) epilogue variants the tile kernels (v2 / v4 / four-wave / W-stationary / halo conv)
 // instantiate: convolutions NONE / SILU, GLU SILU / GELU / GELU_TANH, plain GEMMs every activation.  Any other
 // combination is rejected by every tile config (gemm2_cfg_supported), never run as a neighbouring variant.
@@ -269,9 +283,14 @@ struct AttnArgs {
   // block table, has no bias path.  (Appended: the other fields keep their offsets in the kernels' arguments)
   float k_scale, v_scale;
   int kv_fp8;
+  // > 0: the Q rows of batch b are read from batch b % q_batch_mod (q holds q_batch_mod batches; K / V and O keep B):
+  // one query set attended against several contexts.  flash64_dma / flash64x2 only (flash_q_mod_supported).  (Appended)
+  int q_batch_mod;
 };
 // an fp8 cache (kv_fp8) always takes launch_flash_attn_kv8; bf16 K/V the routing of attention.hip
 void launch_flash_attn(const AttnArgs& a, hipStream_t s);
+// whether launch_flash_attn routes this problem to a kernel that implements q_batch_mod; the caller expands q otherwise
+bool flash_q_mod_supported(const AttnArgs& a);
 // the v1 body with the fp8 cache format (attention_kv8.hip): paged prefill attention straight from the codes
 void launch_flash_attn_kv8(const AttnArgs& a, hipStream_t s);
 // v2 (attention2.hip): 8-wave ping-pong, LDS-DMA K/V ring; launch_flash_attn dispatches to it when supported

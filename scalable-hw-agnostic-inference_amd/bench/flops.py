@@ -40,14 +40,14 @@ def count_flops():
     saved = {n: getattr(ops, n) for n in ("linear", "conv2d", "attention", "bmm", "groupnorm_stats", "layernorm",
                                           "groupnorm_apply", "bias_act", "softmax_")}
 
-    def linear(x, w, bias=None, act=None, residual=None, glu=False, alpha=1.0, res_alpha=1.0):
+    def linear(x, w, bias=None, act=None, residual=None, glu=False, alpha=1.0, res_alpha=1.0, residual_rows=0):
         M = x.numel() // x.shape[-1]
         N, K = w.shape
         fc.add("linear", 2.0 * M * N * K)
         return torch.empty(*x.shape[:-1], N // 2 if glu else N, dtype=x.dtype, device=x.device)
 
     def conv2d(x, w, bias, kh, kw, stride=1, pad=0, upsample=False, x2=None, norm=None, temb=None, residual=None,
-               act=None, res_alpha=1.0):
+               act=None, res_alpha=1.0, residual_rows=0):
         N, H, W, _ = x.shape
         IH, IW = (2 * H, 2 * W) if upsample else (H, W)
         OH = (IH + 2 * pad - kh) // stride + 1
@@ -55,12 +55,14 @@ def count_flops():
         fc.add("conv", 2.0 * N * OH * OW * w.shape[0] * w.shape[1])
         return torch.empty(N, OH, OW, w.shape[0], dtype=x.dtype, device=x.device)
 
-    def attention(q, k, v, scale=None, causal=False, causal_offset=0, kv_lens=None, q_lens=None, bias=None, out=None):
-        B, Sq, H, D = q.shape
+    def attention(q, k, v, scale=None, causal=False, causal_offset=0, kv_lens=None, q_lens=None, bias=None, out=None,
+                  q_batch_mod=0):
+        _, Sq, H, D = q.shape
+        B = k.shape[0] if q_batch_mod else q.shape[0]  # shared queries: one output batch per K/V batch
         Skv = k.shape[1]
         f = 4.0 * B * H * Sq * Skv * D
         fc.add("attention", f / 2 if causal else f)
-        return torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        return torch.empty((B,) + tuple(q.shape[1:]), dtype=q.dtype, device=q.device)
 
     def bmm(a, w, alpha=1.0):
         B, M, K = a.shape

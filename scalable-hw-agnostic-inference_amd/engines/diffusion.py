@@ -76,7 +76,8 @@ class _UNetGraph:
 
     def _fwd(self):
         x = torch.cat([self.lat, self.lat], 0)
-        return self.unet(x, self.t, self.kv)
+        # both guidance halves carry the same latents and timesteps (per_row_t: StepBatcher writes t[j] = t[B + j])
+        return self.unet(x, self.t, self.kv, cfg_pairs=True)
 
     def run(self, t: float) -> torch.Tensor:
         self.t.fill_(t)
@@ -164,7 +165,7 @@ class StableDiffusionEngine:
         else:
             for sp in steps:
                 t = torch.full((1,), sp.t, dtype=torch.float32, device=self.device)
-                out = self.unet(torch.cat([lat, lat], 0), t, ctx_kv)
+                out = self.unet(torch.cat([lat, lat], 0), t, ctx_kv, cfg_pairs=True)
                 ops.sched_step(out, lat, True, guidance_scale, self.scheduler.pred_type, sp.a_t, sp.a_prev)
         with prof.range_("vae_decode"):
             img = self.vae(lat)
@@ -385,7 +386,7 @@ class _Rows:
         self.kv = [torch.zeros(s, dtype=torch.bfloat16, device=device) for s in kv_shapes]
 
     def run_rows(self):
-        return self.unet(torch.cat([self.lat, self.lat], 0), self.t, self.kv)
+        return self.unet(torch.cat([self.lat, self.lat], 0), self.t, self.kv, cfg_pairs=True)
 
 
 def to_pil(img_u8: torch.Tensor):

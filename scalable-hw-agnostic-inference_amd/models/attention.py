@@ -75,12 +75,18 @@ class CrossAttention(nn.Module):
     def context_kv(self, ctx: torch.Tensor) -> torch.Tensor:
         return self.kv(ctx)
 
-    def forward(self, x, ctx_kv: torch.Tensor, residual=None, kv_lens=None):
+    def forward(self, x, ctx_kv: torch.Tensor, residual=None, kv_lens=None, shared: bool = False):
+        """``shared``: x (and the residual) hold B images under a context of n B entries; image b of the output
+        attends with the queries of image b % B and adds residual image b % B."""
         B, T, _ = x.shape
         S = ctx_kv.shape[1]
         H, hd = self.heads, self.head_dim
         q = self.q(x).view(B, T, H, hd)
         k = ctx_kv[..., : H * hd].view(ctx_kv.shape[0], S, H, hd)
         v = ctx_kv[..., H * hd:].view(ctx_kv.shape[0], S, H, hd)
+        if shared:
+            o = ops.attention(q, k, v, kv_lens=kv_lens, q_batch_mod=B)
+            return self.out(o.view(o.shape[0], T, H * hd), residual=residual,
+                            residual_rows=B * T if residual is not None else 0)
         o = ops.attention(q, k, v, kv_lens=kv_lens)
         return self.out(o.view(B, T, H * hd), residual=residual)

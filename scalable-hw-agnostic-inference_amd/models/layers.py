@@ -37,12 +37,14 @@ class Linear(nn.Module):
         self.weight = nn.Parameter(torch.empty(out_features, in_features, dtype=dtype), requires_grad=False)
         self.bias = nn.Parameter(torch.zeros(out_features, dtype=dtype), requires_grad=False) if bias else None
 
-    def forward(self, x, act=None, residual=None, alpha: float = 1.0):
-        return ops.linear(x, self.weight, self.bias, act=act, residual=residual, alpha=alpha)
+    def forward(self, x, act=None, residual=None, alpha: float = 1.0, residual_rows: int = 0):
+        return ops.linear(x, self.weight, self.bias, act=act, residual=residual, alpha=alpha,
+                          residual_rows=residual_rows)
 
-    def forward_stats(self, x, residual=None, stats: str = "ln", eps: float = 1e-5):
+    def forward_stats(self, x, residual=None, stats: str = "ln", eps: float = 1e-5, residual_rows: int = 0):
         """(y, statistics of y for the next norm) -- see ``ops.linear_stats``."""
-        return ops.linear_stats(x, self.weight, self.bias, residual=residual, stats=stats, eps=eps)
+        return ops.linear_stats(x, self.weight, self.bias, residual=residual, stats=stats, eps=eps,
+                                residual_rows=residual_rows)
 
     def folded(self, ln: "LayerNorm"):
         """(w', bias', s) of this projection with LayerNorm ``ln`` folded in (``ops.fold_layernorm``); cached

@@ -5,17 +5,23 @@ runs (cuDNN/Inductor on GPU, NEFF on Inferentia).  MI355X-first design:
 
 * Every 3x3/1x1 conv is the implicit-GEMM MFMA kernel; the time-embedding bias
   and the residual/skip add are fused into the conv epilogue, Upsample2D's
-  nearest-2x is fused into the gather.  A ResNet's GroupNorm+SiLU is the
-  prologue of its 3x3 conv: statistics from the producer's epilogue partials,
-  applied once per staged element in LDS by the halo-tiled conv
-  (csrc/kernels/conv_halo.hip; normalising inside a per-tap gather would repeat
-  the transform 9x per N-tile).
+  nearest-2x is fused into the gather.  A ResNet's GroupNorm+SiLU takes its
+  statistics from the producer's epilogue partials; one vectorised apply pass
+  writes the normalised input and the tuned conv reads it (the default).  The
+  halo-tiled conv (csrc/kernels/conv_halo.hip, ``ops.set_halo_conv``) applies
+  the norm once per staged element in LDS instead; it is opt-in, measured
+  slower at the SD2.1 shapes.
 * Transformer blocks: fused QKV GEMM -> flash attention reading strided views
   -> out-proj GEMM with the residual in its epilogue; GEGLU fused into the FF
   GEMM epilogue.
 * Cross-attention K/V depend only on the text context: computed once per
   request (:meth:`UNet2DConditionModel.context_kv`) and reused for all steps.
 * All 22 ResNet time-embedding projections run as ONE batched GEMM per step.
+* Classifier-free guidance (``forward(..., cfg_pairs=True)``): rows i and B + i
+  of the batch enter identical and stay so until the first cross-attention, so
+  the first ResNet and the first transformer up to its cross-attention Q run on
+  B rows; the kernels that join them with the 2B contexts read the B-row
+  operand in place (``q_batch_mod`` / ``residual_rows``).
 """
 from __future__ import annotations
 
@@ -41,6 +47,14 @@ NORM_HANDOFF = os.environ.get("SHAI_NORM_HANDOFF", "1") != "0"
 # ResNet GroupNorm + SiLU applied by the consuming 3x3 conv (ops.conv2d(norm=...): the halo-tiled conv normalises each
 # staged input element once in LDS); SHAI_FUSED_GN_CONV=0 restores the separate apply pass (A/B)
 FUSED_GN_CONV = os.environ.get("SHAI_FUSED_GN_CONV", "1") != "0"
+# cfg_pairs forwards run the layers both guidance halves share once (UNet2DConditionModel.forward);
+# SHAI_CFG_SHARED=0 restores the full-batch path (A/B)
+CFG_SHARED = os.environ.get("SHAI_CFG_SHARED", "1") != "0"
+# fewest activation rows per guidance half (B H W at the first level) at which the prefix is shared.  One 512^2 image
+# (4096 rows) stays unshared: halving its already small, split-K-bound kernels measured no gain (batch-1 p50 350.7 /
+# 351.3 ms shared against 350.7 / 350.6 ms unshared, profiles/cfg_shared_prefix.md); batch 32 gains 2.7 %.  The gate
+# rests on those two points alone: batches 2 to 16 were not measured
+CFG_SHARED_MIN_ROWS = int(os.environ.get("SHAI_CFG_SHARED_MIN_ROWS", "8192"))
 
 
 @dataclass
@@ -137,18 +151,21 @@ class BasicTransformerBlock(nn.Module):
         self.norm3 = LayerNorm(dim)
         self.ff = FeedForward(dim)
 
-    def forward(self, x, ctx_kv):
+    def forward(self, x, ctx_kv, shared: bool = False):
+        """``shared``: x holds B images under 2B contexts (``CrossAttention.forward``); the output has 2B images."""
         x = self.attn1(self.norm1(x), residual=x)
-        x = self.attn2(self.norm2(x), ctx_kv, residual=x)
+        x = self.attn2(self.norm2(x), ctx_kv, residual=x, shared=shared)
         return self.ff(self.norm3(x), residual=x)
 
-    def forward_folded(self, x, ctx_kv, mr, next_eps=None, defer_down: bool = False):
+    def forward_folded(self, x, ctx_kv, mr, next_eps=None, defer_down: bool = False, shared: bool = False):
         """forward with every LayerNorm folded into the projection that consumes it: ``mr`` = (mean, rstd) [rows, 2]
         of x from its producer; each residual GEMM (attention out-projections, FF down) hands the next norm's
         (mean, rstd) over from its epilogue, so no normalised activation is ever written.  ``next_eps``: the
         following block's norm1 eps (its statistics are returned), None for the last block.  ``defer_down``: return
         (GEGLU output, residual stream) instead of applying the FF down projection (the caller merges it into
-        ``proj_out``)."""
+        ``proj_out``).  ``shared``: x holds B images under a context of 2B entries -- everything up to the
+        cross-attention Q projection runs on B rows; the cross-attention reads Q, and its out-projection the residual
+        stream, of image b % B (``q_batch_mod`` / ``residual_rows``), and the rest runs on 2B rows."""
         B, T, C = x.shape
         a1 = self.attn1
         w, b, s = a1.qkv.folded(self.norm1)
@@ -172,14 +189,17 @@ class BasicTransformerBlock(nn.Module):
             q = ops.linear(x, w, b, row_affine=(mr, s)).view(B, T, H, hd)
         S = ctx_kv.shape[1]
         o = ops.attention(q, ctx_kv[..., : H * hd].view(ctx_kv.shape[0], S, H, hd),
-                          ctx_kv[..., H * hd:].view(ctx_kv.shape[0], S, H, hd))
+                          ctx_kv[..., H * hd:].view(ctx_kv.shape[0], S, H, hd), q_batch_mod=B if shared else 0)
+        rr = B * T if shared else 0  # the residual stream still holds B images
+        B = o.shape[0]
         proj = self.ff.net[0].proj
         if lnout:
             x, xn = ops.linear_lnout(o.view(B, T, H * hd), a2.out.weight, a2.out.bias, x, self.norm3.weight,
-                                     self.norm3.bias, self.norm3.eps)
+                                     self.norm3.bias, self.norm3.eps, residual_rows=rr)
             h = ops.linear(xn, proj.weight, proj.bias, act=proj.act, glu=True)
         else:
-            x, mr = a2.out.forward_stats(o.view(B, T, H * hd), residual=x, stats="ln", eps=self.norm3.eps)
+            x, mr = a2.out.forward_stats(o.view(B, T, H * hd), residual=x, stats="ln", eps=self.norm3.eps,
+                                         residual_rows=rr)
             w, b, s = proj.folded(self.norm3)
             h = ops.linear(x, w, b, act=proj.act, glu=True, row_affine=(mr, s))
         if defer_down:
@@ -198,18 +218,22 @@ class Transformer2DModel(nn.Module):
         self.transformer_blocks = nn.ModuleList([BasicTransformerBlock(channels, heads, ctx_dim)])
         self.proj_out = Linear(channels, channels)
 
-    def forward(self, x, ctx_kv):
+    def forward(self, x, ctx_kv, shared: bool = False):
+        """``shared``: x holds B images under a context of 2B entries; the first block joins them (its output, and
+        this one, have 2B images) and ``proj_out`` adds x of image b % B."""
         B, H, W, C = x.shape
         h = self.proj_in(self.norm(x)).view(B, H * W, C)
-        for blk in self.transformer_blocks:
-            h = blk(h, ctx_kv)
-        return self.proj_out(h, residual=x.view(B, H * W, C)).view(B, H, W, C)
+        for i, blk in enumerate(self.transformer_blocks):
+            h = blk(h, ctx_kv, shared=shared and i == 0)
+        return self.proj_out(h, residual=x.view(B, H * W, C),
+                             residual_rows=B * H * W if shared else 0).view(h.shape[0], H, W, C)
 
-    def forward_parts(self, x, ctx_kv, xp=None, stats: bool = False):
+    def forward_parts(self, x, ctx_kv, xp=None, stats: bool = False, shared: bool = False):
         """forward with the norm hand-offs: GroupNorm partials ``xp`` of x in, LayerNorms folded into the block
         projections (``BasicTransformerBlock.forward_folded``), and with ``stats`` the GroupNorm partials of the
-        output out.  Returns (out, partials or None)."""
+        output out.  Returns (out, partials or None).  ``shared`` as ``forward``."""
         B, H, W, C = x.shape
+        rr = B * H * W if shared else 0  # x, the residual of the output projection, still holds B images
         blocks = list(self.transformer_blocks)
         if ops.fold_profitable(B * H * W, C):  # the Q projection (N = C) has the fewest tiles of the consumers
             if self._gn_fold_ok(x):
@@ -222,18 +246,20 @@ class Transformer2DModel(nn.Module):
             merged = self._merged_out(x.is_cuda)
             for i, blk in enumerate(blocks):
                 if i + 1 == len(blocks) and merged is not None:
-                    ffh, hx = blk.forward_folded(h, ctx_kv, mr, None, defer_down=True)
-                    return self._out_merged(ffh, hx, x, merged, stats)
-                h, mr = blk.forward_folded(h, ctx_kv, mr, blocks[i + 1].norm1.eps if i + 1 < len(blocks) else None)
+                    ffh, hx = blk.forward_folded(h, ctx_kv, mr, None, defer_down=True, shared=shared and i == 0)
+                    return self._out_merged(ffh, hx, x, merged, stats, rr)
+                h, mr = blk.forward_folded(h, ctx_kv, mr, blocks[i + 1].norm1.eps if i + 1 < len(blocks) else None,
+                                           shared=shared and i == 0)
         else:
             h = self.proj_in(self.norm(x, part=xp)).view(B, H * W, C)
-            for blk in blocks:
-                h = blk(h, ctx_kv)
+            for i, blk in enumerate(blocks):
+                h = blk(h, ctx_kv, shared=shared and i == 0)
         res = x.view(B, H * W, C)
+        B = h.shape[0]
         if stats and ops.stats_supported(B * H * W, C, "gn", H * W):
-            out, op = self.proj_out.forward_stats(h, residual=res, stats="gn")
+            out, op = self.proj_out.forward_stats(h, residual=res, stats="gn", residual_rows=rr)
             return out.view(B, H, W, C), op
-        return self.proj_out(h, residual=res).view(B, H, W, C), None
+        return self.proj_out(h, residual=res, residual_rows=rr).view(B, H, W, C), None
 
     def _gn_fold_ok(self, x) -> bool:
         B, H, W, C = x.shape
@@ -278,12 +304,13 @@ class Transformer2DModel(nn.Module):
             self._po_merged = cached
         return cached[1]
 
-    def _out_merged(self, ffh, hx, x, merged, stats):
-        B, H, W, C = x.shape
+    def _out_merged(self, ffh, hx, x, merged, stats, residual_rows: int = 0):
+        _, H, W, C = x.shape
+        B = hx.shape[0]  # more images than x in the shared mode (residual_rows: x is read per image b % its count)
         w, b = merged
         f = ffh.reshape(B, H, W, ffh.shape[-1])
         kw = {"stats": "gn"} if stats and ops.stats_supported(B * H * W, C, "gn", H * W) else {}
-        r = ops.conv2d(f, w, b, 1, 1, x2=hx.reshape(B, H, W, C), residual=x, **kw)
+        r = ops.conv2d(f, w, b, 1, 1, x2=hx.reshape(B, H, W, C), residual=x, residual_rows=residual_rows, **kw)
         return r if kw else (r, None)
 
 
@@ -413,8 +440,15 @@ class UNet2DConditionModel(nn.Module):
         return out
 
     # ------------------------------------------------------------------ forward
-    def forward(self, sample: torch.Tensor, timestep: torch.Tensor, ctx_kv: List[torch.Tensor]) -> torch.Tensor:
-        """sample [B, H, W, 4] NHWC, timestep [B] (float), ctx_kv from :meth:`context_kv`."""
+    def forward(self, sample: torch.Tensor, timestep: torch.Tensor, ctx_kv: List[torch.Tensor],
+                cfg_pairs: bool = False) -> torch.Tensor:
+        """sample [B, H, W, 4] NHWC, timestep [B] (float), ctx_kv from :meth:`context_kv`.
+
+        ``cfg_pairs``: the caller asserts that rows i and B / 2 + i of ``sample`` and of ``timestep`` are equal (the
+        two guidance halves of ``cat([lat, lat])``; only the contexts differ).  They stay equal until the first
+        cross-attention, so the first ResNet of the first down block and its transformer up to the cross-attention Q
+        projection run on the first half only (``CFG_SHARED``).  ``conv_in`` still runs on every row: its output is a
+        skip tensor the last up block reads per image."""
         cfg = self.cfg
         B = sample.shape[0]
         t = timestep.expand(B) if timestep.numel() == 1 else timestep
@@ -426,7 +460,7 @@ class UNet2DConditionModel(nn.Module):
         # silu(emb) then one GEMM for all ResNets
         semb = ops.bias_act(emb, None, None, "silu")
         tall = ops.linear(semb, w, b)
-        tprojs = [tall[:, o:o + n].contiguous() for (o, n) in offs]
+        tprojs = [tall[:, o:o + n] for (o, n) in offs]  # column views: each conv reads its columns of tall in place
         ti = iter(tprojs)
         kvi = iter(ctx_kv)
 
@@ -436,8 +470,18 @@ class UNet2DConditionModel(nn.Module):
         st = NORM_HANDOFF
         x, xp = self.conv_in(sample, stats="gn") if st else (self.conv_in(sample), None)
         skips = [(x, xp)]
-        for blk in self.down_blocks:
+        share = cfg_pairs and self._cfg_share_ok(x)
+        for bi, blk in enumerate(self.down_blocks):
             for i, r in enumerate(blk.resnets):
+                if share and bi == 0 and i == 0:
+                    # the shared prefix: the first-half views of x, of its GroupNorm partials (128-row blocks, whole
+                    # images) and of the time projection; the transformer's cross-attention joins the two contexts
+                    hb = B // 2
+                    x, xp = r.forward_parts(x[:hb], next(ti)[:hb], xp=None if xp is None else xp[: xp.shape[0] // 2],
+                                            stats=st)
+                    x, xp = self._attn(blk.attentions[0], x, next(kvi), xp, st, shared=True)
+                    skips.append((x, xp))
+                    continue
                 x, xp = r.forward_parts(x, next(ti), xp=xp, stats=st)
                 if blk.attentions is not None:
                     x, xp = self._attn(blk.attentions[i], x, next(kvi), xp, st)
@@ -458,11 +502,20 @@ class UNet2DConditionModel(nn.Module):
                 x, xp = blk.upsamplers[0].forward_parts(x, st)
         return self.conv_out(self.conv_norm_out(x, silu=True, part=xp))
 
+    def _cfg_share_ok(self, x) -> bool:
+        """Whether a cfg_pairs forward shares the prefix: an even batch whose first down block has attention, with at
+        least ``CFG_SHARED_MIN_ROWS`` activation rows per half.  (GroupNorm partials exist only for images of whole
+        128-row blocks, so their first half is the first half's partials; where a half is not whole kernel tiles the
+        ops expand the shared operand.)"""
+        B, H, W, _ = x.shape
+        return (CFG_SHARED and B % 2 == 0 and self.down_blocks[0].attentions is not None
+                and (B // 2) * H * W >= CFG_SHARED_MIN_ROWS)
+
     @staticmethod
-    def _attn(t: "Transformer2DModel", x, ctx_kv, xp, st: bool):
+    def _attn(t: "Transformer2DModel", x, ctx_kv, xp, st: bool, shared: bool = False):
         if st:
-            return t.forward_parts(x, ctx_kv, xp=xp, stats=True)
-        return t(x, ctx_kv), None
+            return t.forward_parts(x, ctx_kv, xp=xp, stats=True, shared=shared)
+        return t(x, ctx_kv, shared=shared), None
 
     # ------------------------------------------------------------------ checkpoints
     def convert_hf_state_dict(self, sd: dict) -> dict:

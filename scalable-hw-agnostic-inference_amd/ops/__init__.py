@@ -237,8 +237,13 @@ def gemm_f8(a8: torch.Tensor, w8: torch.Tensor, a_scale: torch.Tensor, w_scale: 
 def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, act=None,
            residual: Optional[torch.Tensor] = None, glu: bool = False, alpha: float = 1.0,
            res_alpha: float = 1.0, rms_eps: Optional[float] = None,
-           w_scale: Optional[torch.Tensor] = None, row_affine=None, force_cfg: int = -1) -> torch.Tensor:
+           w_scale: Optional[torch.Tensor] = None, row_affine=None, force_cfg: int = -1,
+           residual_rows: int = 0) -> torch.Tensor:
     """y = act(alpha * x @ w^T + bias) (+ res_alpha * residual).
+
+    residual_rows > 0: ``residual`` holds that many rows and output row m adds residual row m % residual_rows (a
+    B-image stream under 2B output images).  The v4 / W-stationary kernels read it in place (multiples of 256 / 32
+    rows that divide M); the binding expands it for any other problem.  bf16 weights only.
 
     glu=True: ``w`` rows are interleaved (value_i, gate_i) pairs and the output
     has N/2 columns: value * act(gate) (SwiGLU / GEGLU fused in the epilogue).
@@ -276,9 +281,11 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     if not _gpu(x):
         if rms_eps is not None:
             x = ref.rmsnorm(x, None, rms_eps)[0]
-        return ref.linear(x, w, bias, act, residual, glu, alpha, res_alpha, row_affine=row_affine)
+        return ref.linear(x, w, bias, act, residual, glu, alpha, res_alpha, row_affine=row_affine,
+                          residual_rows=residual_rows)
     if row_affine is not None:
-        return _linear_norm_io(x, w, bias, act, residual, glu, alpha, res_alpha, row_affine, None, 0.0, force_cfg)[0]
+        return _linear_norm_io(x, w, bias, act, residual, glu, alpha, res_alpha, row_affine, None, 0.0, force_cfg,
+                               residual_rows)[0]
     K = x.shape[-1]
     N = w.shape[0]
     lead = x.shape[:-1]
@@ -289,12 +296,16 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     Nout = N // 2 if glu else N
     y = torch.empty(x2.shape[0], Nout, dtype=x.dtype, device=x.device)
     r2 = residual.reshape(-1, Nout) if residual is not None else None
+    # (force_cfg names an fp4 config, or pins the kernel of a broadcast-residual problem for the tests)
     _K().gemm(x2, w, y, bias, None, 1, r2, float(alpha), float(res_alpha), act_id(act), bool(glu), None, 1,
-              int(force_cfg) if is_mxfp4(w) else -1, float(rms_eps) if rms_eps is not None else -1.0, w_scale)
+              int(force_cfg) if (is_mxfp4(w) or residual_rows) else -1,
+              float(rms_eps) if rms_eps is not None else -1.0, w_scale, None, None, None, None, 1e-5, 0,
+              int(residual_rows))
     return y.view(*lead, Nout)
 
 
-def _linear_norm_io(x, w, bias, act, residual, glu, alpha, res_alpha, row_affine, stats, eps, force_cfg=-1):
+def _linear_norm_io(x, w, bias, act, residual, glu, alpha, res_alpha, row_affine, stats, eps, force_cfg=-1,
+                    residual_rows=0):
     K = x.shape[-1]
     x2 = x.reshape(-1, K) if (x.dim() == 2 or x.is_contiguous()) else x.contiguous().reshape(-1, K)
     M, N = x2.shape[0], w.shape[0]
@@ -305,7 +316,7 @@ def _linear_norm_io(x, w, bias, act, residual, glu, alpha, res_alpha, row_affine
     gp = torch.empty(M // 128, Nout, 2, dtype=torch.float32, device=x.device) if stats == "gn" else None
     ls = torch.empty(M, 2, dtype=torch.float32, device=x.device) if stats == "ln" else None
     _K().gemm(x2, w, y, bias, None, 1, r2, float(alpha), float(res_alpha), act_id(act), bool(glu), None, 1,
-              int(force_cfg), -1.0, None, mr, s, gp, ls, float(eps))
+              int(force_cfg), -1.0, None, mr, s, gp, ls, float(eps), 0, int(residual_rows))
     return y.view(*x.shape[:-1], Nout), (gp if stats == "gn" else ls)
 
 
@@ -330,15 +341,17 @@ FOLD_MIN_TILES = int(os.environ.get("SHAI_FOLD_MIN_TILES", "192"))  # tests lowe
 
 
 def linear_stats(x: torch.Tensor, w: torch.Tensor, bias=None, residual=None, act=None, stats: str = "ln",
-                 eps: float = 1e-5, row_affine=None, force_cfg: int = -1):
+                 eps: float = 1e-5, row_affine=None, force_cfg: int = -1, residual_rows: int = 0):
     """``linear`` that also returns statistics of its output for the next norm: stats="ln" -> (mean, rstd) [M, 2]
     with ``eps``; "gn" -> GroupNorm partials [M / 128, N, 2] (``groupnorm_stats_from_partials``).  On the GPU the
     v4 GEMM epilogue writes them (a pass over the output when the tuned kernel cannot)."""
     if not _gpu(x):
-        y = ref.linear(x, w, bias, act, residual, False, 1.0, 1.0, row_affine=row_affine)
+        y = ref.linear(x, w, bias, act, residual, False, 1.0, 1.0, row_affine=row_affine,
+                       residual_rows=residual_rows)
         y2 = y.reshape(-1, y.shape[-1])
         return y, (ref.row_moments(y2, eps) if stats == "ln" else ref.col_partials(y2))
-    return _linear_norm_io(x, w, bias, act, residual, False, 1.0, 1.0, row_affine, stats, eps, force_cfg)
+    return _linear_norm_io(x, w, bias, act, residual, False, 1.0, 1.0, row_affine, stats, eps, force_cfg,
+                           residual_rows)
 
 
 def linear_wslices(x: torch.Tensor, w_slices: torch.Tensor, bias2d: Optional[torch.Tensor], rows_per_slice: int,
@@ -367,22 +380,23 @@ def linear_wslices(x: torch.Tensor, w_slices: torch.Tensor, bias2d: Optional[tor
     return y, (gp if stats == "gn" else ls)
 
 
-def linear_lnout(x: torch.Tensor, w: torch.Tensor, bias, residual: torch.Tensor, gamma, beta, eps: float = 1e-5):
+def linear_lnout(x: torch.Tensor, w: torch.Tensor, bias, residual: torch.Tensor, gamma, beta, eps: float = 1e-5,
+                 residual_rows: int = 0):
     """(y, LayerNorm(y; gamma, beta)) with y = x @ w^T + bias + residual: the next LayerNorm computed by the producing
     GEMM's epilogue (the W-stationary kernel holds whole 320-wide rows: exact two-pass moments of the stored bf16 y),
     so the consumer runs a plain GEMM on the normalised rows.  Falls back to GEMM + standalone LayerNorm wherever
     the fused kernel does not apply (other widths, CPU)."""
     if not _gpu(x):
-        y = ref.linear(x, w, bias, None, residual)
+        y = ref.linear(x, w, bias, None, residual, residual_rows=residual_rows)
         return y, ref.layernorm(y, gamma, beta, eps)[0]
     K, N = x.shape[-1], w.shape[0]
     x2 = x.reshape(-1, K) if (x.dim() == 2 or x.is_contiguous()) else x.contiguous().reshape(-1, K)
     r2 = residual.reshape(-1, N)
     y = torch.empty(x2.shape[0], N, dtype=x.dtype, device=x.device)
     y2 = torch.empty_like(y)
-    if LNOUT and _K().gemm_lnout(x2, w, y, y2, bias, r2, 1.0, gamma, beta, float(eps)):
+    if LNOUT and _K().gemm_lnout(x2, w, y, y2, bias, r2, 1.0, gamma, beta, float(eps), int(residual_rows)):
         return y.view(*x.shape[:-1], N), y2.view(*x.shape[:-1], N)
-    y = linear(x, w, bias, residual=residual)
+    y = linear(x, w, bias, residual=residual, residual_rows=residual_rows)
     return y, layernorm(y, gamma, beta, eps)[0]
 
 
@@ -537,24 +551,35 @@ def up2_phases_ok(x: torch.Tensor, kh: int, kw: int, stride: int, pad: int, x2=N
             and (not grouped or (N % (256 // (H * W)) == 0 and temb is None)))
 
 
+def _bias2d_in_place(t: torch.Tensor) -> bool:
+    """Whether the kernels read this per-image bias where it lies (``GemmArgs::bias2d_ld``): contiguous, or a column
+    slice of a wider matrix whose rows start 16-byte aligned.  Anything else is copied first."""
+    if t.is_contiguous():
+        return True
+    return t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0
+
+
 def conv2d(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor], kh: int, kw: int, stride: int = 1,
            pad: int = 0, upsample: bool = False, x2: Optional[torch.Tensor] = None, norm=None,
            temb: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, act=None,
            res_alpha: float = 1.0, stats: Optional[str] = None, eps: float = 1e-5,
-           w_up2: Optional[torch.Tensor] = None):
+           w_up2: Optional[torch.Tensor] = None, residual_rows: int = 0):
     """NHWC implicit-GEMM convolution with fused prologue/epilogue.
 
     norm = (scale [N,Cin] f32, shift [N,Cin] f32, act) applies GroupNorm(+act) to
     the input: on the GPU one vectorised apply pass + the tuned conv inside the op (``set_halo_conv(1)``: the
     halo-tiled conv normalises each staged element once in LDS instead -- measured slower at the SD2.1 shapes);
     x2 is concatenated on channels; upsample reads a
-    nearest-2x view; temb [N, Cout] is a per-image bias; residual is added last.  w_up2: the phase weights
+    nearest-2x view; temb [N, Cout] is a per-image bias (a column slice of a wider matrix is read in place);
+    residual is added last (residual_rows > 0: it holds that
+    many output pixels and output row m adds residual row m % residual_rows, as ``linear``).  w_up2: the phase weights
     (``pack_up2_phase_weight``) of an upsample conv -- used when ``up2_phases_ok``.
     stats="gn" / "ln": also return statistics of the output for the next norm, as ``linear_stats`` -- (out, st);
     st is None when the output shape cannot carry them (``stats_supported``).
     """
     if not _gpu(x):
-        y = ref.conv2d(x, w_packed, bias, kh, kw, stride, pad, upsample, x2, norm, temb, residual, act, res_alpha)
+        y = ref.conv2d(x, w_packed, bias, kh, kw, stride, pad, upsample, x2, norm, temb, residual, act, res_alpha,
+                       residual_rows)
         if stats is None:
             return y
         y2 = y.reshape(-1, y.shape[-1])
@@ -575,12 +600,15 @@ def conv2d(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor]
         want = stats
     gp = torch.empty(M // 128, cout, 2, dtype=torch.float32, device=x.device) if want == "gn" else None
     ls = torch.empty(M, 2, dtype=torch.float32, device=x.device) if want == "ln" else None
+    if temb is not None and not _bias2d_in_place(temb):
+        temb = temb.contiguous()
     if upsample and w_up2 is not None and up2_phases_ok(x, kh, kw, stride, pad, x2, norm, residual, temb=temb):
         _K().conv2d(x, None, w_up2, out, bias, temb, None, None, None, 0, 2, 2, 1, 0, True, act_id(act), 1.0, None,
                     None, gp, ls, float(eps), True)
     else:
         _K().conv2d(x, x2, w_packed, out, bias, temb, residual, sc, sh, act_id(nact), kh, kw, stride, pad,
-                    bool(upsample), act_id(act), float(res_alpha), None, None, gp, ls, float(eps))
+                    bool(upsample), act_id(act), float(res_alpha), None, None, gp, ls, float(eps), False,
+                    int(residual_rows))
     if stats is None:
         return out
     return out, (gp if want == "gn" else ls)
@@ -588,16 +616,19 @@ def conv2d(x: torch.Tensor, w_packed: torch.Tensor, bias: Optional[torch.Tensor]
 
 # ----------------------------------------------------------------------------- attention
 def attention(q, k, v, scale: Optional[float] = None, causal: bool = False, causal_offset: int = 0, kv_lens=None,
-              q_lens=None, bias=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Fused flash attention. q [B,Sq,Hq,D] (packed heads), k/v [B,Skv,Hkv,D]."""
+              q_lens=None, bias=None, out: Optional[torch.Tensor] = None, q_batch_mod: int = 0) -> torch.Tensor:
+    """Fused flash attention. q [B,Sq,Hq,D] (packed heads), k/v [B,Skv,Hkv,D].  q_batch_mod > 0: q holds q_batch_mod
+    batches and batch b of k / v / the output attends with the queries of batch b % q_batch_mod (read in place by the
+    D = 64 LDS-DMA kernels, expanded by the binding for any other)."""
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     if not _gpu(q):
-        o = ref.attention(q, k, v, scale, causal, causal_offset, kv_lens, q_lens, bias)
+        o = ref.attention(q, k, v, scale, causal, causal_offset, kv_lens, q_lens, bias, q_batch_mod)
         return out.copy_(o) if out is not None else o
-    o = out if out is not None else torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    oshape = (k.shape[0],) + tuple(q.shape[1:]) if q_batch_mod else q.shape
+    o = out if out is not None else torch.empty(oshape, dtype=q.dtype, device=q.device)
     _K().flash_attn(q, k, v, o, float(scale), bool(causal), int(causal_offset), _i32(kv_lens), _i32(q_lens), bias,
-                    None)
+                    None, 1.0, 1.0, int(q_batch_mod))
     return o
 
 

@@ -121,7 +121,16 @@ def groupnorm_apply(x, scale, shift, silu):
     return y.to(x.dtype)
 
 
-def linear(x, w, bias=None, act=None, residual=None, glu=False, alpha=1.0, res_alpha=1.0, row_affine=None):
+def wrap_rows(t, rows, cols):
+    """Broadcast operand by index arithmetic: row m of the [rows, cols] result is row m % t_rows of t."""
+    t2 = t.reshape(-1, cols)
+    assert rows % t2.shape[0] == 0, "the broadcast operand's rows must divide the output rows"
+    return t2[torch.arange(rows, device=t.device) % t2.shape[0]]
+
+
+def linear(x, w, bias=None, act=None, residual=None, glu=False, alpha=1.0, res_alpha=1.0, row_affine=None,
+           residual_rows=0):
+    """residual_rows > 0: the residual holds that many rows, and output row m adds residual row m % residual_rows."""
     y = torch.matmul(x.float(), w.float().t())
     if row_affine is not None:  # LayerNorm folded in: rstd[m] * (x w'^T - mean[m] * s[n])
         mr, s = row_affine
@@ -137,7 +146,10 @@ def linear(x, w, bias=None, act=None, residual=None, glu=False, alpha=1.0, res_a
     else:
         y = apply_act(y, act)
     if residual is not None:
-        y = y + res_alpha * residual.float()
+        r = residual.float()
+        if residual_rows:
+            r = wrap_rows(r, y.numel() // y.shape[-1], y.shape[-1]).reshape(y.shape)
+        y = y + res_alpha * r
     return y.to(x.dtype)
 
 
@@ -310,8 +322,9 @@ def conv2d_up2_phases(x, w_phase, bias=None, temb=None, act=None):
 
 
 def conv2d(x, w_packed, bias, kh, kw, stride=1, pad=0, upsample=False, x2=None, norm=None, temb=None,
-           residual=None, act=None, res_alpha=1.0):
-    """x NHWC [N,H,W,C1] (+x2 [N,H,W,C2] concatenated on C) -> NHWC output."""
+           residual=None, act=None, res_alpha=1.0, residual_rows=0):
+    """x NHWC [N,H,W,C1] (+x2 [N,H,W,C2] concatenated on C) -> NHWC output.  residual_rows > 0: the residual holds
+    that many output pixels (rows), and output row m adds residual row m % residual_rows."""
     xin = x.float() if x2 is None else torch.cat([x.float(), x2.float()], dim=-1)
     if norm is not None:
         scale, shift, nact = norm
@@ -330,12 +343,20 @@ def conv2d(x, w_packed, bias, kh, kw, stride=1, pad=0, upsample=False, x2=None, 
         y = y + temb.float()[:, None, None, :]
     y = apply_act(y, act)
     if residual is not None:
-        y = y + res_alpha * residual.float().reshape(y.shape)
+        r = residual.float()
+        if residual_rows:
+            r = wrap_rows(r, y.numel() // y.shape[-1], y.shape[-1])
+        y = y + res_alpha * r.reshape(y.shape)
     return y.to(x.dtype)
 
 
-def attention(q, k, v, scale=None, causal=False, causal_offset=0, kv_lens=None, q_lens=None, bias=None):
-    """q [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] -> [B,Sq,Hq,D]."""
+def attention(q, k, v, scale=None, causal=False, causal_offset=0, kv_lens=None, q_lens=None, bias=None,
+              q_batch_mod=0):
+    """q [B,Sq,Hq,D], k/v [B,Skv,Hkv,D] -> [B,Sq,Hq,D].  q_batch_mod > 0: q holds q_batch_mod batches and batch b of
+    the output (k / v's batch) attends with the queries of batch b % q_batch_mod."""
+    if q_batch_mod:
+        assert q.shape[0] == q_batch_mod and k.shape[0] % q_batch_mod == 0
+        q = q[torch.arange(k.shape[0], device=q.device) % q_batch_mod]
     B, Sq, Hq, D = q.shape
     Skv, Hkv = k.shape[1], k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
