@@ -452,53 +452,100 @@ __global__ void __launch_bounds__(256) gn_finalize_kernel(const float* __restric
 }
 
 // Apply pass, y = (silu)(x * scale[n, c] + shift[n, c]) over channels-last [N, HW, C] (two sources: channels
-// [0, C1) from x, [C1, C) from x2).  The launcher makes the grid's thread count a multiple of C / 8, so every
-// thread keeps ONE 8-channel vector for the whole grid-stride loop: its scale / shift (4 x 16 B) are loaded once
-// per image instead of once per 16 B of x, and the pixel index advances by a constant -- no 64-bit division per
-// element group (both dominated the old loop's issue).
-__global__ void __launch_bounds__(256) gn_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ x2,
-                                                       int C1, const float* __restrict__ scale,
-                                                       const float* __restrict__ shift, bf16_t* __restrict__ out,
-                                                       long total8, int HW, int C, int silu) {
-  const int C8 = C >> 3, C18 = C1 >> 3, C28 = (C - C1) >> 3;
-  const long stride = (long)gridDim.x * blockDim.x;  // a multiple of C8
-  long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
-  if (i >= total8) return;
-  const int cv = (int)(i % C8);
-  long pix = i / C8;
-  const long pstep = stride / C8;
-  int n = (int)(pix / HW);
-  long next = (long)(n + 1) * HW;
+// [0, C1) from x, [C1, C) from x2), streamed with kGnApplyLoads independent 16-byte loads in flight per thread.
+//
+// Work split: a workgroup owns one RUN, `run` consecutive pixels of ONE image, over one SLAB of `W` consecutive
+// 8-channel vectors (W = C / 8 when that fits 256 threads, else C / 8 split into `slabs` near-equal parts).  Its
+// threads are P = 256 / W pixel lanes x W vectors, so with one slab the workgroup's loads and stores of one step
+// are one contiguous span of the tensor.  A thread keeps its channel vector for the whole run: blockIdx is taken
+// apart (image, run, slab) and scale / shift (4 x 16 B) and the source (x or x2, with its row width) are fetched
+// once, before the loop; the loop itself only advances two pointers by constants -- no division, no reload, no
+// image boundary (a run never leaves its image).  `SILU` is a template parameter.
+//
+// Grid (launch_groupnorm_apply): one workgroup per (image, run, slab), slab fastest so neighbouring workgroups
+// touch neighbouring memory, and a run is ONE step, kGnApplyLoads * P pixels (about 15 KB read and written): the
+// grid follows from the shape alone.  Measured on MI355X (profiles/gn_apply_stream.md): runs of 2, 4 or 16 steps,
+// with the length taken from the tensor's bytes over the CU count, and 2 or 8 loads per thread, were all slower
+// at every SD2.1 UNet and VAE shape; short runs also spread the 8 x 8 level and the VAE mid blocks over every CU.
+// The loop is kept so that a tensor of more than 2^31 - 1 steps still gets a legal grid (longer runs).  Offsets
+// are 64-bit: one VAE tensor exceeds 2^31 bytes.  At most 64 VGPRs (8 waves per SIMD), no scratch.
+constexpr int kGnApplyLoads = 4;
+
+template <int U, bool SILU>
+__global__ void __launch_bounds__(256, 8) gn_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ x2,
+                                                          int C1, const float* __restrict__ scale,
+                                                          const float* __restrict__ shift, bf16_t* __restrict__ out,
+                                                          long total8, int HW, int C, int W, int slabs, int run,
+                                                          int runs_per_image) {
+  const int C8 = C >> 3, C18 = C1 >> 3, C28 = C8 - C18;
+  const int t = threadIdx.x;
+  // once per workgroup: blockIdx -> (image n, run r, slab sl)
+  const unsigned sl = blockIdx.x % (unsigned)slabs, br = blockIdx.x / (unsigned)slabs;
+  const int r = (int)(br % (unsigned)runs_per_image), n = (int)(br / (unsigned)runs_per_image);
+  const int P = 256 / W;
+  const int pl = t / W;
+  const int cv = (int)sl * W + (t - pl * W);
+  if (pl >= P || cv >= C8) return;
+  const int p0 = r * run;
+  const int p1 = min(HW, p0 + run);
   const bool first = cv < C18;
-  const uint4_* src = first ? reinterpret_cast<const uint4_*>(x) + cv : reinterpret_cast<const uint4_*>(x2) + (cv - C18);
-  const int srcw = first ? C18 : C28;
-  float4_ a0, a1, b0, b1;
-  auto load_ss = [&]() {
-    const float* sc = scale + (long)n * C + cv * 8;
-    const float* sh = shift + (long)n * C + cv * 8;
-    a0 = *reinterpret_cast<const float4_*>(sc);
-    a1 = *reinterpret_cast<const float4_*>(sc + 4);
-    b0 = *reinterpret_cast<const float4_*>(sh);
-    b1 = *reinterpret_cast<const float4_*>(sh + 4);
+  const int ld = first ? C18 : C28;  // source row width in vectors
+  const long img = (long)n * HW;     // first pixel of the image, in pixels of the whole tensor
+  const uint4_* sp = (first ? reinterpret_cast<const uint4_*>(x) + cv : reinterpret_cast<const uint4_*>(x2) + (cv - C18)) +
+                     (img + p0 + pl) * ld;
+  uint4_* op = reinterpret_cast<uint4_*>(out) + (img + p0 + pl) * C8 + cv;
+  const long sstep = (long)P * ld, ostep = (long)P * C8;
+  const float* sc = scale + (long)n * C + cv * 8;
+  const float* sh = shift + (long)n * C + cv * 8;
+  const float4_ a0 = *reinterpret_cast<const float4_*>(sc), a1 = *reinterpret_cast<const float4_*>(sc + 4);
+  const float4_ b0 = *reinterpret_cast<const float4_*>(sh), b1 = *reinterpret_cast<const float4_*>(sh + 4);
+  // debug flavour: pixel p of this run is inside the tensor and inside image n
+  auto check = [&](int p) {
+    SHAI_DASSERT((img + p) * C8 + cv < total8);
+    SHAI_DASSERT((img + p) / HW == n);
+    (void)p;
   };
-  load_ss();
-  for (; i < total8; i += stride, pix += pstep) {
-    if (pix >= next) {  // crossed into another image (rare unless HW is small)
-      n = (int)(pix / HW);
-      next = (long)(n + 1) * HW;
-      load_ss();
-    }
+  auto apply = [&](const uint4_ v) {
     float f[8];
-    unpack8(src[pix * srcw], f);
+    unpack8(v, f);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       f[k] = f[k] * a0[k] + b0[k];
       f[k + 4] = f[k + 4] * a1[k] + b1[k];
     }
-    if (silu)
+    if constexpr (SILU) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) f[k] = silu_f(f[k]);
-    reinterpret_cast<uint4_*>(out)[i] = pack8(f);
+    }
+    return pack8(f);
+  };
+  // ONE loop body for full steps and the run's tail (a second, scalar tail loop made the compiler keep a second
+  // arrangement of scale / shift and spill; predicated stores made it sink a load into its branch): at the
+  // thread's last pixel of the run both pointers stop advancing, so the rest of a short step reads that pixel again
+  // and stores the same 16 bytes again.  Straight-line code, and only the last step of a run can be short.
+  for (int p = p0 + pl; p < p1; p += U * P) {
+    uint4_ v[U];
+    int q = p;  // the pixel sp points at (debug checks)
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      check(q);
+      v[u] = *sp;
+      const bool more = p + (u + 1) * P < p1;
+      sp += more ? sstep : 0;
+      q += more ? P : 0;
+    }
+    // one vector at a time behind the loads: interleaving the U applies holds 8 U floats and spills
+    q = p;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      __builtin_amdgcn_sched_barrier(0);
+      check(q);
+      *op = apply(v[u]);
+      const bool more = p + (u + 1) * P < p1;
+      op += more ? ostep : 0;
+      q += more ? P : 0;
+    }
+    __builtin_amdgcn_sched_barrier(0);
   }
 }
 
@@ -530,17 +577,28 @@ void launch_groupnorm_stats(const GroupNormArgs& a, hipStream_t s) {
 }
 
 void launch_groupnorm_apply(const GroupNormArgs& a, hipStream_t s) {
+  constexpr int U = kGnApplyLoads;
   const long total8 = (long)a.N * a.HW * a.C / 8;
-  long blocks = (total8 + 255) / 256;
-  if (blocks > 4096) blocks = 4096;
-  // grid threads a multiple of C / 8 (the kernel keeps one channel vector per thread)
+  if (total8 == 0) return;
   const int C8 = a.C / 8;
-  int g = C8, b = 256;
-  while (b) { const int t = g % b; g = b; b = t; }  // gcd(C8, 256)
-  const long unit = C8 / g;
-  blocks = (blocks + unit - 1) / unit * unit;
-  gn_apply_kernel<<<(int)blocks, 256, 0, s>>>(a.x, a.x2, a.x2 ? a.C1 : a.C, a.scale, a.shift, a.out, total8, a.HW,
-                                              a.C, a.silu);
+  const int slabs = (C8 + 255) / 256;
+  const int W = (C8 + slabs - 1) / slabs;  // <= 256 vectors per slab
+  const int P = 256 / W;
+  const int threads = (P * W + 63) / 64 * 64;
+  long run = (long)U * P, rpi = (a.HW + run - 1) / run;  // one step of U loads per thread and run
+  while ((long)a.N * rpi * slabs > 0x7fffffffL) {  // (never at real sizes) keep the grid inside 31 bits
+    run *= 2;
+    rpi = (a.HW + run - 1) / run;
+  }
+  if (run > a.HW) run = a.HW;  // one run per image: `run` stays an int
+  const unsigned grid = (unsigned)((long)a.N * rpi * slabs);
+  const int C1 = a.x2 ? a.C1 : a.C;
+  if (a.silu)
+    gn_apply_kernel<U, true><<<grid, threads, 0, s>>>(a.x, a.x2, C1, a.scale, a.shift, a.out, total8, a.HW, a.C, W,
+                                                     slabs, (int)run, (int)rpi);
+  else
+    gn_apply_kernel<U, false><<<grid, threads, 0, s>>>(a.x, a.x2, C1, a.scale, a.shift, a.out, total8, a.HW, a.C, W,
+                                                      slabs, (int)run, (int)rpi);
 }
 
 
