@@ -287,9 +287,11 @@ def test_flash2_varlen_strided_gqa(cuda, D, causal):
 
 @pytest.mark.parametrize("causal", [False, True])
 def test_flash2_d64_long_spikes_varlen(cuda, causal):
-    """flash2 at D = 64 (Sq, Skv >= 2048: the SD2.1 self-attention kernel, pre-scaled Q and max-folded score
-    accumulators): spikes in the first tile and past the fast-path bound, a moderate max growth, per-batch
-    lengths with a partial last query tile, GQA 2:1."""
+    """D = 64 at Sq, Skv >= 2048 (the SD2.1 self-attention shape).  With default settings this runs flash64-DMA
+    (launch_flash64: 9 * 4 * 2 = 72 workgroups of 256 queries, below flash64x2's 1024); flash2<64> takes the shape
+    only under SHAI_FLASH64=0 (tests/test_attn_edges_gpu.py::test_knob_only_kernels runs it there).  Spikes in the
+    first tile and past the fast-path bound, a moderate max growth, per-batch lengths with a partial last query
+    tile, GQA 2:1."""
     torch.manual_seed(16)
     B, S, Hq, Hkv, D = 2, 2200, 4, 2, 64
     q, k, v = rnd(B, S, Hq, D), rnd(B, S, Hkv, D), rnd(B, S, Hkv, D)
