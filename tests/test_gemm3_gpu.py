@@ -4,6 +4,11 @@
 * gemm_w4.hip (four-wave, one 128x128 wave tile per SIMD): config 13 (256x256) -- in production for the VAE
   decoder convs and the LLM prefill / Flux shapes, so every epilogue it implements is forced here too
   (test_w4_* below).
+
+The tests here judge a whole tensor by its relative Frobenius error, which one wrong row, column quad or image corner
+passes.  The every-element check of the same kernels and configs is tests/test_gemm_exact_gpu.py: integer inputs for
+which the output must equal bf16(fp64 result) bit for bit, poison around every operand, canaries around every output
+(tests/gemm_exact.py).
 """
 import os
 import subprocess
