@@ -1783,6 +1783,77 @@ void sample(const Tensor& logits, const Tensor& temps, const Tensor& top_k, cons
                       out.data_ptr<int>(), stream());
 }
 
+// the fused sampler with penalties and min_p (launch_sample_penalized): state [rows, V] int32 or none
+void sample_penalized(const Tensor& logits, const Tensor& temps, const Tensor& top_k, const Tensor& top_p,
+                      const Tensor& uniforms, const Tensor& out, const optional<Tensor>& state,
+                      const Tensor& state_rows, const Tensor& rep, const Tensor& freq, const Tensor& pres,
+                      const Tensor& min_p) {
+  SHAI_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be a 2D GPU tensor");
+  const bool bf16 = logits.scalar_type() == at::kBFloat16;
+  SHAI_CHECK(bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or fp32");
+  const int B = logits.size(0);
+  const long V = logits.size(1);
+  check_f32(temps, "temps");
+  check_f32(top_p, "top_p");
+  check_f32(uniforms, "uniforms");
+  check_i32(top_k, "top_k");
+  check_i32(out, "out");
+  check_i32(state_rows, "state_rows");
+  check_f32(rep, "repetition_penalty");
+  check_f32(freq, "frequency_penalty");
+  check_f32(pres, "presence_penalty");
+  check_f32(min_p, "min_p");
+  SHAI_CHECK(temps.numel() == B && top_p.numel() == B && uniforms.numel() == B && top_k.numel() == B &&
+                 out.numel() == B && state_rows.numel() == B && rep.numel() == B && freq.numel() == B &&
+                 pres.numel() == B && min_p.numel() == B,
+             "per-row parameter sizes");
+  int* st = nullptr;
+  int n_rows = 0;
+  if (state.has_value()) {
+    check_i32(*state, "state");
+    SHAI_CHECK(state->dim() == 2 && state->size(1) == V, "penalty state must be [rows, V] int32 with the logits' V");
+    st = state->data_ptr<int>();
+    n_rows = state->size(0);
+  }
+  shai::launch_sample_penalized(logits.data_ptr(), bf16, logits.stride(0), B, V, temps.data_ptr<float>(),
+                                top_k.data_ptr<int>(), top_p.data_ptr<float>(), uniforms.data_ptr<float>(),
+                                out.data_ptr<int>(), st, n_rows, state_rows.data_ptr<int>(), rep.data_ptr<float>(),
+                                freq.data_ptr<float>(), pres.data_ptr<float>(), min_p.data_ptr<float>(), stream());
+}
+
+void penalty_state_init(const Tensor& state, int64_t row, const Tensor& tokens, int64_t n_prompt) {
+  check_i32(state, "state");
+  check_i32(tokens, "tokens");
+  SHAI_CHECK(state.dim() == 2 && row >= 0 && row < state.size(0), "penalty_state_init: row ", row, " of ",
+             state.dim() == 2 ? state.size(0) : -1, " state rows");
+  SHAI_CHECK(tokens.dim() == 1 && n_prompt >= 0, "penalty_state_init: tokens must be 1-D, n_prompt >= 0");
+  const long V = state.size(1);
+  shai::launch_penalty_state_init(state.data_ptr<int>() + row * V, V, tokens.numel() ? tokens.data_ptr<int>() : nullptr,
+                                  (int)tokens.numel(), (int)std::min<int64_t>(n_prompt, tokens.numel()), stream());
+}
+
+void token_logprobs(const Tensor& logits, const Tensor& toks, const optional<Tensor>& row_n, const Tensor& vals,
+                    const Tensor& ids) {
+  SHAI_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be a 2D GPU tensor");
+  const bool bf16 = logits.scalar_type() == at::kBFloat16;
+  SHAI_CHECK(bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or fp32");
+  const int B = logits.size(0);
+  check_i32(toks, "tokens");
+  check_f32(vals, "vals");
+  check_i32(ids, "ids");
+  SHAI_CHECK(vals.dim() == 2 && vals.size(0) == B && vals.size(1) >= 1 && vals.size(1) <= 1 + 1024 &&
+                 ids.sizes() == vals.sizes() && toks.numel() == B,
+             "token_logprobs: vals / ids must be [B, 1 + N] with N <= 1024, tokens [B]");
+  const int* rn = nullptr;
+  if (row_n.has_value()) {
+    check_i32(*row_n, "row_n");
+    SHAI_CHECK(row_n->numel() == B, "row_n must hold one count per row");
+    rn = row_n->data_ptr<int>();
+  }
+  shai::launch_token_logprobs(logits.data_ptr(), bf16, logits.stride(0), B, logits.size(1), toks.data_ptr<int>(), rn,
+                              (int)vals.size(1) - 1, vals.data_ptr<float>(), ids.data_ptr<int>(), stream());
+}
+
 void rope_pairs(const Tensor& x, const Tensor& cos, const Tensor& sin) {
   check_bf16(x, "x");
   check_f32(cos, "cos");
@@ -2042,6 +2113,10 @@ TORCH_LIBRARY(shai, m) {
   m.def("rope(Tensor(a!) x, Tensor positions, Tensor cos, Tensor sin, int rot_dim, bool neox) -> ()");
   m.def("rope_pairs(Tensor(a!) x, Tensor cos, Tensor sin) -> ()");
   m.def("sample(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out) -> ()");
+  m.def("sample_penalized(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out, "
+        "Tensor(b!)? state, Tensor state_rows, Tensor rep, Tensor freq, Tensor pres, Tensor min_p) -> ()");
+  m.def("penalty_state_init(Tensor(a!) state, int row, Tensor tokens, int n_prompt) -> ()");
+  m.def("token_logprobs(Tensor logits, Tensor tokens, Tensor? row_n, Tensor(a!) vals, Tensor(b!) ids) -> ()");
   m.def("rope_qkv_cache(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor slots, int H, int Hkv, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("sched_step(Tensor model_out, Tensor(a!) latents, bool cfg, float guidance, int pred_type, float a_t, float a_prev, float dt) -> ()");
   m.def("sched_step_rows(Tensor model_out, Tensor(a!) latents, bool cfg, float guidance, int pred_type, Tensor rows_params) -> ()");
@@ -2088,6 +2163,9 @@ TORCH_LIBRARY_IMPL(shai, CUDA, m) {
   m.impl("rope", &rope);
   m.impl("rope_pairs", &rope_pairs);
   m.impl("sample", &sample);
+  m.impl("sample_penalized", &sample_penalized);
+  m.impl("penalty_state_init", &penalty_state_init);
+  m.impl("token_logprobs", &token_logprobs);
   m.impl("rope_qkv_cache", &rope_qkv_cache);
   m.impl("sched_step", &sched_step);
   m.impl("sched_step_rows", &sched_step_rows);

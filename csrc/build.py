@@ -48,7 +48,10 @@ NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8",
               # the native fp8 paged prefill attention (flash_v1.h's body with the fp8 format, D = 64 and 128)
               "kernels/attention_kv8.hip": "flash_fwd_kernelINS_5KvFp8",
               # the fp4 tile GEMM holds up to 128 accumulators beside the widened fragments: every instantiation
-              "kernels/gemm_fp4.hip": "gemm_fp4_kernel"}
+              "kernels/gemm_fp4.hip": "gemm_fp4_kernel",
+              # the samplers (plain and penalised) and the log-probability kernel: every instantiation
+              "kernels/sampling.hip": ("sample_kernel", "token_logprobs_kernel")}
+NO_SCRATCH_NAMES = [p for v in NO_SCRATCH.values() for p in ((v,) if isinstance(v, str) else v)]
 # per-source extra hipcc flags: gemm_w4's epilogue (256 accumulators x an activation) is larger than LLVM's
 # default pragma-unroll budget; partially unrolled it would index the accumulators at run time (scratch)
 EXTRA_KFLAGS = {"kernels/attention3.hip": "-mllvm -amdgpu-mfma-vgpr-form -fno-slp-vectorize",
@@ -163,7 +166,7 @@ def check_no_scratch(log: str) -> list:
         if "Function Name:" in ln:
             fn = ln.split("Function Name:", 1)[1].split()[0]
             seen = True
-            if not any(pat in fn for pat in NO_SCRATCH.values()):
+            if not any(pat in fn for pat in NO_SCRATCH_NAMES):
                 fn = None
         elif fn and "ScratchSize [bytes/lane]:" in ln:
             checked.append(fn)
@@ -172,7 +175,7 @@ def check_no_scratch(log: str) -> list:
     if bad:
         raise RuntimeError("kernels that must not use scratch memory spill: " + "; ".join(bad))
     if seen and not checked:
-        raise RuntimeError("the no-scratch check found none of its kernels (" + ", ".join(NO_SCRATCH.values()) +
+        raise RuntimeError("the no-scratch check found none of its kernels (" + ", ".join(NO_SCRATCH_NAMES) +
                            ") in the resource-usage remarks")
     return checked
 

@@ -373,4 +373,19 @@ void launch_kv_write(const bf16_t* k, const bf16_t* v, bf16_t* k_cache, bf16_t* 
 // Per-row temperature / top-k (<= 1024 candidates) / top-p sampling from bf16 or fp32 logits [B, ld].
 void launch_sample(const void* logits, bool bf16, long ld, int B, int V, const float* temps, const int* top_k,
                    const float* top_p, const float* uniforms, int* out, hipStream_t s);
+// The same with penalties and min_p.  state: [n_state_rows, V] int32 penalty-state words (bit 30: the token occurs in
+// the prompt; bits 0..29: how often it was sampled) or null; state_rows[b]: row b's state row, -1 for none.  The
+// logits of a row with a state row are penalised (repetition rep, frequency freq, presence pres) before sampling, and
+// the picked token's count is incremented.  Candidates with exp((l_i - l_0) / T) < min_p are dropped before top-p.
+void launch_sample_penalized(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                             const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                             int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                             const float* pres, const float* min_p, hipStream_t s);
+// Clear one state row (V words) and scatter a token list into it: the first n_prompt tokens set the prompt flag, the
+// rest count as sampled.  Ids outside [0, V) are ignored.
+void launch_penalty_state_init(int* state_row, int V, const int* tokens, int n_tokens, int n_prompt, hipStream_t s);
+// Log-softmax of the raw logits: vals / ids [B, 1 + N], entry 0 at toks[b], entries 1..N the N largest (descending
+// value, ascending index).  row_n (or null): per-row count <= N, negative = skip the row.
+void launch_token_logprobs(const void* logits, bool bf16, long ld, int B, int V, const int* toks, const int* row_n,
+                           int N, float* vals, int* ids, hipStream_t s);
 }  // namespace shai

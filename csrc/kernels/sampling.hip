@@ -14,6 +14,13 @@
 //      as the torch reference path), draw with a host-supplied uniform.
 // Temperature <= 0 rows are greedy (K = 1).  Same distribution as
 // shai_amd.engines.llm.sample(); the uniforms come from the engine's generator.
+//
+// The penalised instantiation (launch_sample_penalized) is the same body with three additions: the logit load
+// applies the repetition / frequency / presence penalties from the row's penalty-state words (one int32 per
+// vocabulary entry: bit 30 = the token occurs in the prompt, bits 0..29 = how often it was sampled), stage 4 drops
+// the candidates with p_i < min_p before the nucleus cut, and the picked token's count is incremented at the end,
+// so the state is current in stream order for the next (look-ahead) step.  Steps 1-3 are shared, as device
+// functions, with token_logprobs_kernel (log-softmax of the raw logits at the picked token and at the top N).
 #include "common.h"
 #include "launchers.h"
 
@@ -22,6 +29,8 @@ namespace shai {
 constexpr int SMP_T = 1024;          // threads per row
 constexpr int SMP_MAXK = 1024;       // candidates kept in LDS
 constexpr int SMP_WAVES = SMP_T / 64;
+constexpr int PEN_PROMPT = 1 << 30;  // penalty-state word: prompt flag; the bits below it count sampled occurrences
+constexpr int PEN_COUNT = PEN_PROMPT - 1;
 
 __device__ __forceinline__ uint32_t f2key(float f) {
   const uint32_t u = __float_as_uint(f);
@@ -34,27 +43,50 @@ __device__ __forceinline__ float smp_load(const void* row, int i) {
   else return reinterpret_cast<const float*>(row)[i];
 }
 
+// the raw logits of one row
 template <bool BF16>
-__global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ logits, long ld, int V,
-                                                       const float* __restrict__ temps, const int* __restrict__ topk,
-                                                       const float* __restrict__ topp,
-                                                       const float* __restrict__ uniforms, int* __restrict__ out) {
+struct RawLoad {
+  const char* base;
+  __device__ __forceinline__ float operator()(int i) const { return smp_load<BF16>(base, i); }
+};
+
+// the penalised logits of one row (st: its state words, or null): every pass of the sampler re-reads the row
+// through this one function, and contraction is off in it, so every pass sees the same value -- the value the
+// fp32 oracle computes (IEEE division; no fma across the penalty steps)
+template <bool BF16>
+struct PenLoad {
+  const char* base;
+  const int* st;
+  float r, f, p;
+  __device__ __forceinline__ float operator()(int i) const {
+#pragma clang fp contract(off)
+    float l = smp_load<BF16>(base, i);
+    if (st) {
+      const int wd = st[i];
+      if (wd != 0) {
+        const int c = wd & PEN_COUNT;
+        l = l > 0.f ? l / r : l * r;
+        const float fc = f * (float)c;
+        l = l - fc;
+        if (c > 0) l = l - p;
+      }
+    }
+    return l;
+  }
+};
+
+// Steps 1-3 for one row: the K largest values of load(0..V-1) into cval / cidx (SMP_MAXK entries each), sorted by
+// descending value then ascending index; returns how many (K, 1 <= K <= min(V, SMP_MAXK)).  KEY16: the values are
+// widened bf16 (two radix digits fix the threshold).  All SMP_T threads of the workgroup call it together.
+template <bool KEY16, class Load>
+__device__ __forceinline__ int smp_topk(const Load& load, int V, int K, float* cval, int* cidx) {
   // 4 histogram copies per wave (by lane & 3): logits crowd into a few exponent bins, and same-address LDS
   // atomics of one wave instruction serialise -- the copies cut the worst case from 64-way to 16-way
   __shared__ uint32_t hist[SMP_WAVES][4][256];
   __shared__ uint32_t tot[256];
-  __shared__ float cval[SMP_MAXK];
-  __shared__ int cidx[SMP_MAXK];
-  __shared__ float scan[SMP_MAXK];
   __shared__ uint32_t s_prefix, s_k, s_cnt, s_eq;
-  const int row = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const char* base = reinterpret_cast<const char*>(logits) + (long)row * ld * (BF16 ? 2 : 4);
-  const float T = temps[row];
-  int K = topk[row];
-  if (T <= 0.f) K = 1;
-  if (K <= 0 || K > V) K = V;
-  K = min(K, SMP_MAXK);
-
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  SHAI_DASSERT(K >= 1 && K <= V && K <= SMP_MAXK);
   // ---- 1. radix select: key threshold with count(key > thr) < K <= count(key >= thr)
   if (tid == 0) {
     s_prefix = 0;
@@ -62,13 +94,13 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
   }
   uint32_t mask = 0;
   // bf16 logits: the low 16 bits of a key are fixed by its sign, so the top two digits already fix the threshold
-  for (int pass = 3; pass >= (BF16 ? 2 : 0); --pass) {
+  for (int pass = 3; pass >= (KEY16 ? 2 : 0); --pass) {
     for (int i = tid; i < SMP_WAVES * 4 * 256; i += SMP_T) (&hist[0][0][0])[i] = 0;
     __syncthreads();
     const uint32_t prefix = s_prefix;
     const int sh = 8 * pass;
     for (int i = tid; i < V; i += SMP_T) {
-      const uint32_t key = f2key(smp_load<BF16>(base, i));
+      const uint32_t key = f2key(load(i));
       if ((key & mask) == prefix) atomicAdd(&hist[w][lane & 3][(key >> sh) & 255], 1u);
     }
     __syncthreads();
@@ -95,7 +127,7 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
   }
   uint32_t thr = s_prefix;
   // (bf16: a negative value's key has its low 16 bits all ones, a positive value's all zeros)
-  if (BF16 && !(thr & 0x80000000u)) thr |= 0xFFFFu;
+  if (KEY16 && !(thr & 0x80000000u)) thr |= 0xFFFFu;
   const uint32_t ties = s_k;  // how many elements equal to thr to keep
   // ---- 2. gather exactly K candidates: every key above the threshold, and of the keys equal to it the
   // `ties` with the lowest vocabulary indices (deterministic; when every equal key is kept no ordering is
@@ -104,7 +136,7 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
   if (tid == 0) s_cnt = 0;
   __syncthreads();
   for (int i = tid; i < V; i += SMP_T) {
-    const float v = smp_load<BF16>(base, i);
+    const float v = load(i);
     const uint32_t key = f2key(v);
     if (key > thr || (all_ties && key == thr)) {
       const uint32_t slot = atomicAdd(&s_cnt, 1u);
@@ -122,7 +154,7 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
     uint32_t mine = 0;
     for (int i0 = c0; i0 < c1; i0 += 64) {
       const int i = i0 + lane;
-      mine += __popcll(__ballot(i < c1 && f2key(smp_load<BF16>(base, i)) == thr));
+      mine += __popcll(__ballot(i < c1 && f2key(load(i)) == thr));
     }
     if (lane == 0) tie_cnt[w] = mine;
     __syncthreads();
@@ -131,7 +163,7 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
     const uint32_t above = s_cnt;
     for (int i0 = c0; i0 < c1 && rank0 < ties; i0 += 64) {
       const int i = i0 + lane;
-      const float v = i < c1 ? smp_load<BF16>(base, i) : 0.f;
+      const float v = i < c1 ? load(i) : 0.f;
       const bool eq = i < c1 && f2key(v) == thr;
       const unsigned long long bal = __ballot(eq);
       const uint32_t rank = rank0 + __popcll(bal & ((1ull << lane) - 1ull));
@@ -146,6 +178,7 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
   }
   __syncthreads();
   const int n = min((int)s_cnt, SMP_MAXK);
+  SHAI_DASSERT(n == K);
   int P = 1;
   while (P < n) P <<= 1;
   for (int i = tid; i < P; i += SMP_T)
@@ -179,13 +212,75 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
       __syncthreads();
     }
   }
+  return n;
+}
+
+// per-row penalty inputs of the penalised sampler (rows: index into the state table, -1 = the row has none)
+struct PenArgs {
+  int* state;       // [n_rows, V] int32, or null
+  int n_rows;
+  const int* rows;
+  const float *rep, *freq, *pres, *minp;
+};
+
+template <bool BF16, bool PEN>
+__global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ logits, long ld, int V,
+                                                       const float* __restrict__ temps, const int* __restrict__ topk,
+                                                       const float* __restrict__ topp,
+                                                       const float* __restrict__ uniforms, int* __restrict__ out,
+                                                       PenArgs pa) {
+  __shared__ float cval[SMP_MAXK];
+  __shared__ int cidx[SMP_MAXK];
+  __shared__ float scan[SMP_MAXK];
+  const int row = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const char* base = reinterpret_cast<const char*>(logits) + (long)row * ld * (BF16 ? 2 : 4);
+  const float T = temps[row];
+  int K = topk[row];
+  if (T <= 0.f) K = 1;
+  if (K <= 0 || K > V) K = V;
+  K = min(K, SMP_MAXK);
+
+  int* st = nullptr;  // this row's state words
+  float minp = 0.f;
+  int n;
+  if constexpr (PEN) {
+    const int srow = pa.rows[row];
+    SHAI_DASSERT(srow < pa.n_rows);
+    if (pa.state && srow >= 0 && srow < pa.n_rows) st = pa.state + (long)srow * V;
+    minp = pa.minp[row];
+    const PenLoad<BF16> load{base, st, pa.rep[row], pa.freq[row], pa.pres[row]};
+    n = smp_topk<false>(load, V, K, cval, cidx);
+  } else {
+    const RawLoad<BF16> load{base};
+    n = smp_topk<BF16>(load, V, K, cval, cidx);
+  }
   if (T <= 0.f || n == 1) {
-    if (tid == 0) out[row] = cidx[0];
+    if (tid == 0) {
+      const int tok = cidx[0];
+      out[row] = tok;
+      if constexpr (PEN) {
+        SHAI_DASSERT(tok >= 0 && tok < V);
+        if (st && tok >= 0 && tok < V) atomicAdd(&st[tok], 1);
+      }
+    }
     return;
   }
-  // ---- 4. probabilities, inclusive scan, nucleus cut, draw
+  // ---- 4. probabilities, (min_p cut,) inclusive scan, nucleus cut, draw
   const float inv_t = 1.f / T, l0 = cval[0];
-  const float p = tid < n ? __expf((cval[tid] - l0) * inv_t) : 0.f;
+  float p = tid < n ? __expf((cval[tid] - l0) * inv_t) : 0.f;
+  if constexpr (PEN) {
+    // min_p: candidates with p_i < min_p go (p_0 = 1 stays); p falls along the sorted candidates, so they are a
+    // suffix and the survivors are the first n2
+    __shared__ int s_n2;
+    if (tid == 0) s_n2 = 0;
+    __syncthreads();
+    const bool stay = tid < n && (tid == 0 || !(p < minp));
+    if (stay) atomicAdd(&s_n2, 1);
+    else p = 0.f;
+    __syncthreads();
+    n = max(1, min(n, s_n2));
+    if (tid >= n) p = 0.f;
+  }
   // block inclusive scan (wave scan + wave totals)
   float x = p;
 #pragma unroll
@@ -224,13 +319,115 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
   __syncthreads();
   if (tid < L - 1 && scan[tid] <= target) atomicAdd(&s_pick, 1);
   __syncthreads();
-  if (tid == 0) out[row] = cidx[min(s_pick, L - 1)];
+  if (tid == 0) {
+    const int tok = cidx[min(s_pick, L - 1)];
+    out[row] = tok;
+    if constexpr (PEN) {
+      SHAI_DASSERT(tok >= 0 && tok < V);
+      if (st && tok >= 0 && tok < V) atomicAdd(&st[tok], 1);
+    }
+  }
 }
 
 void launch_sample(const void* logits, bool bf16, long ld, int B, int V, const float* temps, const int* top_k,
                    const float* top_p, const float* uniforms, int* out, hipStream_t s) {
-  if (bf16) sample_kernel<true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out);
-  else sample_kernel<false><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out);
+  const PenArgs none{};
+  if (bf16) sample_kernel<true, false><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, none);
+  else sample_kernel<false, false><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, none);
+}
+
+void launch_sample_penalized(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                             const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                             int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                             const float* pres, const float* min_p, hipStream_t s) {
+  const PenArgs pa{state, n_state_rows, state_rows, rep, freq, pres, min_p};
+  if (bf16) sample_kernel<true, true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa);
+  else sample_kernel<false, true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa);
+}
+
+// ---- penalty state: (re)initialise one row.  Workgroup b owns PSI_SPAN consecutive words: it clears them, then
+// walks the token list and applies the tokens that fall into its span (prompt tokens set the flag, the others
+// count), so one launch needs no ordering between workgroups.  Ids outside [0, V) fall into no span.
+constexpr int PSI_T = 256;
+constexpr int PSI_SPAN = 4096;
+
+__global__ void __launch_bounds__(PSI_T) penalty_state_init_kernel(int* __restrict__ st, int V,
+                                                                   const int* __restrict__ tokens, int n_tokens,
+                                                                   int n_prompt) {
+  const int lo = blockIdx.x * PSI_SPAN, hi = min(V, lo + PSI_SPAN);
+  for (int i = lo + threadIdx.x; i < hi; i += PSI_T) st[i] = 0;
+  __syncthreads();
+  for (int j = threadIdx.x; j < n_tokens; j += PSI_T) {
+    const int t = tokens[j];
+    if (t >= lo && t < hi) {
+      SHAI_DASSERT(t >= 0 && t < V);
+      if (j < n_prompt) atomicOr(&st[t], PEN_PROMPT);
+      else atomicAdd(&st[t], 1);
+    }
+  }
+}
+
+void launch_penalty_state_init(int* state_row, int V, const int* tokens, int n_tokens, int n_prompt, hipStream_t s) {
+  penalty_state_init_kernel<<<(V + PSI_SPAN - 1) / PSI_SPAN, PSI_T, 0, s>>>(state_row, V, tokens, n_tokens, n_prompt);
+}
+
+// ---- log-probabilities of the raw logits, one workgroup per row: vals / ids [B, 1 + N]; entry 0 is the picked
+// token (toks[row]), entries 1..N the N most likely tokens (descending value, ascending index).  row_n (optional):
+// how many of the N this row wants; a negative value skips the row, the entries past it read -inf / -1.
+// max and sum exp(l - max) in a fixed order (per-thread partial over i = tid, tid + 1024, ...; wave butterfly; the
+// 16 wave results in sequence), so the result does not vary between runs.
+template <bool BF16>
+__global__ void __launch_bounds__(SMP_T) token_logprobs_kernel(const void* __restrict__ logits, long ld, int V,
+                                                               const int* __restrict__ toks,
+                                                               const int* __restrict__ row_n, int N,
+                                                               float* __restrict__ vals, int* __restrict__ ids) {
+  __shared__ float cval[SMP_MAXK];
+  __shared__ int cidx[SMP_MAXK];
+  __shared__ float red[SMP_WAVES];
+  const int row = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  int want = row_n ? min(row_n[row], N) : N;
+  if (want < 0) return;
+  const RawLoad<BF16> load{reinterpret_cast<const char*>(logits) + (long)row * ld * (BF16 ? 2 : 4)};
+  float m = -INFINITY;
+  for (int i = tid; i < V; i += SMP_T) m = fmaxf(m, load(i));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if (lane == 0) red[w] = m;
+  __syncthreads();
+  float mx = red[0];
+#pragma unroll
+  for (int q = 1; q < SMP_WAVES; ++q) mx = fmaxf(mx, red[q]);
+  __syncthreads();
+  float s = 0.f;
+  for (int i = tid; i < V; i += SMP_T) s += __expf(load(i) - mx);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) red[w] = s;
+  __syncthreads();
+  float sum = red[0];
+#pragma unroll
+  for (int q = 1; q < SMP_WAVES; ++q) sum += red[q];
+  const float lse = mx + logf(sum);
+  const long o0 = (long)row * (1 + N);
+  if (tid == 0) {
+    const int tok = toks[row];
+    SHAI_DASSERT(tok >= 0 && tok < V);
+    vals[o0] = tok >= 0 && tok < V ? load(tok) - lse : -INFINITY;
+    ids[o0] = tok;
+  }
+  int n = 0;
+  if (want > 0) n = smp_topk<BF16>(load, V, min(want, V), cval, cidx);
+  if (tid < N) {
+    SHAI_DASSERT(n <= N);
+    vals[o0 + 1 + tid] = tid < n ? cval[tid] - lse : -INFINITY;
+    ids[o0 + 1 + tid] = tid < n ? cidx[tid] : -1;
+  }
+}
+
+void launch_token_logprobs(const void* logits, bool bf16, long ld, int B, int V, const int* toks, const int* row_n,
+                           int N, float* vals, int* ids, hipStream_t s) {
+  if (bf16) token_logprobs_kernel<true><<<B, SMP_T, 0, s>>>(logits, ld, V, toks, row_n, N, vals, ids);
+  else token_logprobs_kernel<false><<<B, SMP_T, 0, s>>>(logits, ld, V, toks, row_n, N, vals, ids);
 }
 
 }  // namespace shai

@@ -33,6 +33,7 @@ from __future__ import annotations
 import hashlib
 import itertools
 import math
+import numbers
 import os
 import time
 from dataclasses import dataclass, field
@@ -58,6 +59,31 @@ class SamplingParams:
     stop_token_ids: Optional[List[int]] = None
     ignore_eos: bool = False
     seed: Optional[int] = None
+    # vLLM's further request-level options, all neutral by default (validated in LLMEngine.add_request)
+    repetition_penalty: float = 1.0      # > 0; seen tokens (prompt or output): l / r if l > 0 else l * r
+    presence_penalty: float = 0.0        # [-2, 2]; subtracted once from every token the sequence has sampled
+    frequency_penalty: float = 0.0       # [-2, 2]; subtracted per sampled occurrence
+    min_p: float = 0.0                   # [0, 1]; candidates below min_p x the top probability are dropped (before top-p)
+    logprobs: Optional[int] = None       # None, or 0..20 top log-probabilities per generated token
+
+    @property
+    def penalised(self) -> bool:
+        """Whether the sequence needs a penalty-state row."""
+        return self.repetition_penalty != 1.0 or self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+
+    def validate(self) -> None:
+        num = lambda x: isinstance(x, numbers.Real) and not isinstance(x, bool) and math.isfinite(x)
+        if not (num(self.repetition_penalty) and self.repetition_penalty > 0):
+            raise ValueError(f"repetition_penalty must be > 0, got {self.repetition_penalty!r}")
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if not (num(v) and -2.0 <= v <= 2.0):
+                raise ValueError(f"{name} must be in [-2, 2], got {v!r}")
+        if not (num(self.min_p) and 0.0 <= self.min_p <= 1.0):
+            raise ValueError(f"min_p must be in [0, 1], got {self.min_p!r}")
+        n = self.logprobs
+        if n is not None and not (isinstance(n, numbers.Integral) and not isinstance(n, bool) and 0 <= n <= ops.LOGPROBS_MAX):
+            raise ValueError(f"logprobs must be None or an integer in 0..{ops.LOGPROBS_MAX}, got {n!r}")
 
 
 @dataclass(eq=False)  # identity semantics: membership tests must not deep-compare prompts (O(B^2))
@@ -78,6 +104,9 @@ class Sequence_:
     finish_time: Optional[float] = None
     finished: bool = False
     finish_reason: Optional[str] = None
+    n_prompt0: int = 0                                           # original prompt length (preemption grows ``prompt``)
+    pen_row: int = -1                                            # row of the engine's penalty-state table, -1: none
+    logprobs: List[dict] = field(default_factory=list)           # one entry per output token (params.logprobs set)
 
     @property
     def tokens(self) -> List[int]:
@@ -184,11 +213,17 @@ class _DecodeGraph:
     previous decode step's output (``engine.last_tokens``) instead of the host id.  This is what lets the
     engine enqueue step t+1 before it has read step t's tokens back (``LLMEngine.async_decode``)."""
 
-    NF = 9  # per-row int32 fields before the block table
+    NF = 9  # per-row int32 fields before the block table (6 more in a penalised / logprobs program)
 
     def __init__(self, engine: "LLMEngine", Bc: int, cross: bool = False, greedy: bool = False,
-                 splits: Optional[int] = None, full_vocab: bool = False):
+                 splits: Optional[int] = None, full_vocab: bool = False, pen: int = 0, lp: bool = False):
         self.Bc = Bc
+        # pen: 0 today's sampler; 1 the penalised sampler without a state table (min_p only); 2 with the table (its
+        # address is captured).  lp: the log-probability kernel runs after the sampler.  Either adds the per-row
+        # fields state row / repetition / frequency / presence / min_p / logprobs count to the step's buffer.
+        self.pen, self.lp = pen, lp
+        if pen or lp:
+            self.NF = 15
         # full_vocab: some row samples with top_k <= 0 (or > 1024) -- the fused sampler keeps 1024 candidates,
         # so such steps publish the logits from the graph and sample them exactly over the whole vocabulary
         # (torch top-k / top-p path, same inverse-CDF rule at the same uniforms) after the replay
@@ -202,6 +237,14 @@ class _DecodeGraph:
         self.ids, self.pos, self.slots, self.lens, self.topk = f(0), f(1), f(2), f(3), f(4)
         self.temps, self.topp, self.u = f(5).view(torch.float32), f(6).view(torch.float32), f(7).view(torch.float32)
         self.rowmap = f(8)
+        if pen or lp:
+            self.prow, self.nlp = f(9), f(14)
+            self.rep, self.freq, self.pres, self.minp = (f(i).view(torch.float32) for i in (10, 11, 12, 13))
+            self.prow.fill_(-1)
+            self.nlp.fill_(-1)
+            self.rep.fill_(1.0)
+        if lp:   # [2, Bc, 1 + N]: log-probabilities (fp32 bits) and token ids, one device->host copy per step
+            self.lp_buf = torch.zeros(2, Bc, 1 + ops.LOGPROBS_MAX, dtype=torch.int32, device=dev)
         self.bt = self.dbuf[self.NF * Bc:].view(Bc, mb)
         self.slots.fill_(-1)
         self.lens.fill_(1)
@@ -248,11 +291,24 @@ class _DecodeGraph:
             return
         if self.greedy:
             self.toks.copy_(logits.float().argmax(-1))
+        elif self.pen:
+            self._sample_pen(logits)
         elif logits.is_cuda:   # full_vocab=False: no host-side inspection of the (captured) top-k values
             sample(logits, self.temps, self.topk, self.topp, uniforms=self.u, out=self.toks, full_vocab=False)
         else:
             self.toks.copy_(sample(logits, self.temps, self.topk, self.topp, uniforms=self.u))
         eng.last_tokens[:self.Bc].copy_(self.toks)
+        if self.lp:
+            self._logprobs(logits)
+
+    def _sample_pen(self, logits, full_vocab=False):
+        ops.sample_penalized(logits, self.temps, self.topk, self.topp, self.u, self.toks,
+                             self.engine.pen_state if self.pen == 2 else None, self.prow, self.rep, self.freq,
+                             self.pres, self.minp, full_vocab=full_vocab)
+
+    def _logprobs(self, logits):
+        ops.token_logprobs(logits, self.toks, ops.LOGPROBS_MAX, self.nlp, self.lp_buf[0].view(torch.float32),
+                           self.lp_buf[1])
 
     def launch(self, seqs, pos, slots, lens, bt, ids, rowmap, uniforms, cross=None):
         """Enqueue one decode step; returns (host int32 token view, completion event or None)."""
@@ -272,6 +328,19 @@ class _DecodeGraph:
         v(6).view(np.float32)[:B] = [s.params.top_p for s in seqs]
         v(7).view(np.float32)[:B] = uniforms
         v(8)[:B] = rowmap
+        if self.pen or self.lp:
+            v(9)[:B] = [s.pen_row for s in seqs]
+            v(10).view(np.float32)[:B] = [s.params.repetition_penalty for s in seqs]
+            v(11).view(np.float32)[:B] = [s.params.frequency_penalty for s in seqs]
+            v(12).view(np.float32)[:B] = [s.params.presence_penalty for s in seqs]
+            v(13).view(np.float32)[:B] = [s.params.min_p for s in seqs]
+            v(14)[:B] = [-1 if s.params.logprobs is None else s.params.logprobs for s in seqs]
+            if B < Bc:  # padding rows: no state row, neutral penalties, no logprobs
+                v(9)[B:] = -1
+                v(10).view(np.float32)[B:] = 1.0
+                for k in (11, 12, 13):
+                    v(k).view(np.float32)[B:] = 0.0
+                v(14)[B:] = -1
         btv = h[self.NF * Bc:].reshape(Bc, -1)
         btv[:B] = bt
         if B < Bc:  # padding rows: no KV write, one-token context, greedy, no feedback
@@ -309,24 +378,34 @@ class _DecodeGraph:
             self._program()
         eng = self.engine
         if self.full_vocab:   # exact full-vocabulary top-k / top-p at the same uniforms, outside the graph
-            self.toks.copy_(sample(self.logits, self.temps, self.topk, self.topp, uniforms=self.u, full_vocab=True))
+            if self.pen:      # ... with penalties and min_p: the oracle's rule on the device, state counted too
+                self._sample_pen(self.logits, full_vocab=True)
+            else:
+                self.toks.copy_(sample(self.logits, self.temps, self.topk, self.topp, uniforms=self.u,
+                                       full_vocab=True))
             eng.last_tokens[:self.Bc].copy_(self.toks)
+            if self.lp:
+                self._logprobs(self.logits)
         out = eng.tok_host[eng.tok_flip][:Bc]
+        lp_out = None
+        if self.lp:   # the logprobs ride beside the tokens, in a pinned buffer of their own behind the same event
+            lp_out = eng.lp_host_buf(eng.tok_flip)[:self.lp_buf.numel()].view(self.lp_buf.shape)
+            lp_out.copy_(self.lp_buf, non_blocking=True)
         eng.tok_flip ^= 1
         out.copy_(self.toks, non_blocking=True)
         done = None
         if self.dbuf.is_cuda:
             done = torch.cuda.Event()
             done.record()
-        return out, done
+        return out, done, lp_out
 
 
 class _Inflight:
     """A decode step that has been enqueued but whose tokens the host has not consumed yet."""
-    __slots__ = ("seqs", "toks", "event", "cross")
+    __slots__ = ("seqs", "toks", "event", "cross", "lp")
 
-    def __init__(self, seqs, toks, event, cross):
-        self.seqs, self.toks, self.event, self.cross = seqs, toks, event, cross
+    def __init__(self, seqs, toks, event, cross, lp=None):
+        self.seqs, self.toks, self.event, self.cross, self.lp = seqs, toks, event, cross, lp
 
 
 KV_CACHE_DTYPES = {"auto": torch.bfloat16, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16,
@@ -460,6 +539,12 @@ class LLMEngine:
         pin = self.device.type == "cuda"
         self.tok_host = [torch.zeros(bmax, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
         self.tok_flip = 0
+        # penalty state (repetition / presence / frequency penalties): one int32 word per (row, vocabulary entry),
+        # allocated by the first penalised request and never moved (decode graphs capture its address); rows are
+        # handed to penalised sequences on admission and come back with their KV blocks
+        self.pen_state: Optional[torch.Tensor] = None
+        self._pen_free: List[int] = list(range(max_num_seqs - 1, -1, -1))
+        self._lp_host: Optional[List[torch.Tensor]] = None
         self.stats = {"prefill_tokens": 0, "decode_tokens": 0, "steps": 0, "prefix_hit_tokens": 0}
         self.eos = {cfg.eos_token_id}
 
@@ -530,6 +615,9 @@ class LLMEngine:
         """image: PIL image / HWC uint8 array / preprocess_image() dict (multimodal models only); the prompt
         gets an ``<|image|>`` token after BOS if it has none."""
         params = params or SamplingParams()
+        params.validate()
+        if params.penalised and self.pen_state is None:
+            self._alloc_pen_state()
         prompt = list(prompt)[-(self.max_model_len - 1):] or [self.cfg.bos_token_id]
         img = None
         pos = -1
@@ -545,9 +633,35 @@ class LLMEngine:
             pos = prompt.index(itok)
         sid = next(self._ids)
         key = (int(params.seed) & ((1 << 63) - 1)) | (1 << 63) if params.seed is not None else (self.seed << 32) + sid
-        s = Sequence_(sid, prompt, params, image=img, img_pos=pos, rng_key=key)
+        s = Sequence_(sid, prompt, params, image=img, img_pos=pos, rng_key=key, n_prompt0=len(prompt))
         self.waiting.append(s)
         return s
+
+    def _alloc_pen_state(self) -> None:
+        V, n = self.cfg.vocab_size, self.max_num_seqs
+        try:
+            self.pen_state = torch.zeros(n, V, dtype=torch.int32, device=self.device)
+        except (RuntimeError, MemoryError) as e:   # torch.OutOfMemoryError is a RuntimeError
+            self.pen_state = None
+            raise MemoryError(f"no room for the penalty-state table ({n} x {V} int32 = {4 * n * V / 2**20:.0f} MiB); "
+                              "lower gpu_memory_utilization or max_num_seqs, or send the request without "
+                              f"repetition / presence / frequency penalties: {e}") from None
+
+    def lp_host_buf(self, i: int) -> torch.Tensor:
+        """Pinned host buffer ``i`` (of two) for a step's logprobs, allocated with the first request that asks."""
+        if self._lp_host is None:
+            n = 2 * self.last_tokens.numel() * (1 + ops.LOGPROBS_MAX)
+            self._lp_host = [torch.zeros(n, dtype=torch.int32, pin_memory=self.device.type == "cuda")
+                             for _ in range(2)]
+        return self._lp_host[i]
+
+    def _pen_attach(self, s: Sequence_) -> None:
+        """Give an admitted penalised sequence a state row and (re)build it from the host-known tokens: the
+        original prompt flags, everything sampled since (a preempted sequence carries it in ``prompt``) counts."""
+        if not s.params.penalised or s.pen_row >= 0:
+            return
+        s.pen_row = self._pen_free.pop()
+        ops.penalty_state_init(self.pen_state, s.pen_row, s.tokens, s.n_prompt0)
 
     def has_work(self) -> bool:
         return bool(self.waiting or self.running or self._inflight is not None)
@@ -583,6 +697,9 @@ class LLMEngine:
         self.bm.release(s.blocks + s.cross_blocks)
         s.blocks = []
         s.cross_blocks = []
+        if s.pen_row >= 0:   # (a look-ahead step still in flight may count one more token in the row: the next
+            self._pen_free.append(s.pen_row)   # owner's init launch clears it, later in stream order)
+            s.pen_row = -1
 
     def _prefix_hashes(self, toks: Sequence[int], n_full: int) -> List[int]:
         hs, h = [], 0
@@ -630,6 +747,7 @@ class LLMEngine:
                 continue
             s.prefill_started = True
             s._hashes = []
+            self._pen_attach(s)
             if self.prefix_caching and s.image is None:  # image prompts: K/V depend on the image, not cached
                 n_full = (len(s.prompt) - 1) // KV_BLOCK
                 hs = self._prefix_hashes(s.prompt, n_full)
@@ -762,21 +880,43 @@ class LLMEngine:
         pos, slots, lens, bt = build_decode(ctx_before, [s.blocks for s in seqs], self.max_blocks)
         Bc = 1 << max(0, math.ceil(math.log2(B)))
         cross = self._cross_tables(seqs) if any(s.cross_blocks for s in seqs) else None
-        greedy = all(s.params.temperature <= 0 for s in seqs)
+        all_greedy = all(s.params.temperature <= 0 for s in seqs)
+        pen, lp = self._pen_kind(seqs), any(s.params.logprobs is not None for s in seqs)
+        greedy = all_greedy and not pen   # greedy rows of a penalised batch need penalised logits: the sampler
         splits = self.decode_splits(Bc, int(lens.max()) if B else 0)
-        full = (not greedy) and any(s.params.temperature > 0 and not 0 < s.params.top_k <= ops.SAMPLER_MAX_K
-                                    for s in seqs)
+        full = (not all_greedy) and any(s.params.temperature > 0 and not 0 < s.params.top_k <= ops.SAMPLER_MAX_K
+                                        for s in seqs)
         key = (Bc, cross is not None, greedy, splits) + ((True,) if full else ())
+        if pen or lp:   # (steps with neither keep the keys and programs they always had)
+            key += (("pen", pen, "logprobs", lp),)
         g = self._graphs.get(key)
         if g is None:
             g = self._graphs[key] = _DecodeGraph(self, Bc, cross=cross is not None, greedy=greedy, splits=splits,
-                                                 full_vocab=full)
+                                                 full_vocab=full, pen=pen, lp=lp)
         # noise for the token each row samples, at absolute position ctx_before + 1
-        u = (seq_uniforms([s.rng_key for s in seqs], [c + 1 for c in ctx_before]) if not greedy
+        u = (seq_uniforms([s.rng_key for s in seqs], [c + 1 for c in ctx_before]) if not all_greedy
              else np.zeros(B, np.float32))
-        toks, ev = g.launch(seqs, pos, slots, lens, bt, ids, rowmap, u, cross)
+        toks, ev, lps = g.launch(seqs, pos, slots, lens, bt, ids, rowmap, u, cross)
         self.stats["decode_tokens"] += B
-        return _Inflight(seqs, toks, ev, cross is not None)
+        return _Inflight(seqs, toks, ev, cross is not None, lps)
+
+    @staticmethod
+    def _pen_kind(seqs) -> int:
+        """Which sampler a batch needs: 2 some row holds a penalty-state row, 1 min_p only, 0 today's."""
+        if any(s.pen_row >= 0 for s in seqs):
+            return 2
+        return 1 if any(s.params.min_p > 0 for s in seqs) else 0
+
+    @staticmethod
+    def _lp_entries(seqs, vals, ids):
+        """Per sequence its logprobs entry from host [B, 1 + N] values / ids (None where it asked for none)."""
+        out = []
+        for i, s in enumerate(seqs):
+            n = s.params.logprobs
+            out.append(None if n is None else {"token": int(ids[i, 0]), "logprob": float(vals[i, 0]),
+                                               "top_ids": [int(t) for t in ids[i, 1:1 + n]],
+                                               "top_logprobs": [float(x) for x in vals[i, 1:1 + n]]})
+        return out
 
     def _finish_decode(self, h: _Inflight):
         """Consume an enqueued decode step's tokens (rows of sequences that finished meanwhile -- the
@@ -784,10 +924,16 @@ class LLMEngine:
         if h.event is not None:
             h.event.synchronize()
         toks = h.toks[:len(h.seqs)].tolist()
-        live = [(s, t) for s, t in zip(h.seqs, toks) if not s.finished]
-        for s, _ in live:
+        lps = [None] * len(toks)
+        if h.lp is not None:
+            lps = self._lp_entries(h.seqs, h.lp[0].view(torch.float32).numpy(), h.lp[1].numpy())
+        live = [(s, t, e) for s, t, e in zip(h.seqs, toks, lps) if not s.finished]
+        for s, _, _ in live:
             s.n_cached = s.length
-        self._append([s for s, _ in live], [t for _, t in live])
+        if h.lp is None:
+            self._append([s for s, _, _ in live], [t for _, t, _ in live])
+        else:
+            self._append([s for s, _, _ in live], [t for _, t, _ in live], [e for _, _, e in live])
 
     def _lookahead(self, prev: _Inflight) -> Optional[_Inflight]:
         """Enqueue the next decode step before ``prev``'s tokens are read back, feeding ``prev``'s sampled
@@ -825,13 +971,41 @@ class LLMEngine:
         greedy = all(s.params.temperature <= 0 for s in seqs)
         u = None if greedy else torch.from_numpy(seq_uniforms([s.rng_key for s in seqs],
                                                               [s.length for s in seqs])).to(d)
-        toks = sample(logits, temps, tk, tpp, self.gen, all_greedy=greedy, uniforms=u).tolist()
-        self._append(seqs, toks)
+        pen, lp = self._pen_kind(seqs), any(s.params.logprobs is not None for s in seqs)
+        if not pen and not lp:
+            self._append(seqs, sample(logits, temps, tk, tpp, self.gen, all_greedy=greedy, uniforms=u).tolist())
+            return
+        # the same ops as the decode program: penalised sampler (counts the picked tokens), then logprobs
+        f32 = lambda xs: torch.tensor(xs, dtype=torch.float32, device=d)
+        toks = torch.empty(len(seqs), dtype=torch.int32, device=d)
+        if pen:
+            full = any(s.params.temperature > 0 and not 0 < s.params.top_k <= ops.SAMPLER_MAX_K for s in seqs)
+            ops.sample_penalized(logits, temps, tk.int(), tpp, u if u is not None else torch.zeros_like(temps), toks,
+                                 self.pen_state if pen == 2 else None,
+                                 torch.tensor([s.pen_row for s in seqs], dtype=torch.int32, device=d),
+                                 f32([s.params.repetition_penalty for s in seqs]),
+                                 f32([s.params.frequency_penalty for s in seqs]),
+                                 f32([s.params.presence_penalty for s in seqs]),
+                                 f32([s.params.min_p for s in seqs]), full_vocab=full)
+        else:
+            toks.copy_(sample(logits, temps, tk, tpp, self.gen, all_greedy=greedy, uniforms=u))
+        lps = None
+        if lp:
+            nlp = torch.tensor([-1 if s.params.logprobs is None else s.params.logprobs for s in seqs],
+                               dtype=torch.int32, device=d)
+            vals, ids = ops.token_logprobs(logits, toks, ops.LOGPROBS_MAX, nlp)
+            lps = self._lp_entries(seqs, vals.cpu().numpy(), ids.cpu().numpy())
+        if lps is None:
+            self._append(seqs, toks.tolist())
+        else:
+            self._append(seqs, toks.tolist(), lps)
 
-    def _append(self, seqs, toks):
+    def _append(self, seqs, toks, lps=None):
         now = time.perf_counter()
-        for s, tok in zip(seqs, toks):
+        for i, (s, tok) in enumerate(zip(seqs, toks)):
             s.output.append(int(tok))
+            if lps is not None and lps[i] is not None:
+                s.logprobs.append(lps[i])
             if s.first_token_time is None:
                 s.first_token_time = now
             stop = set(s.params.stop_token_ids or []) | (set() if s.params.ignore_eos else self.eos)

@@ -29,6 +29,7 @@ __all__ = [
     "ACT_GELU_TANH", "ACT_QUICK_GELU", "ACT_RELU", "decode_splits", "set_decode_wb",
     "paged_attention_varlen", "rope_qkv_cache", "quantize_kv_fp8", "dequant_kv_fp8", "kv_dequant_blocks",
     "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE", "resolve_kv_prefill", "KV_PREFILL_ROUTES",
+    "sample_penalized", "penalty_state_init", "token_logprobs", "LOGPROBS_MAX",
 ]
 
 
@@ -975,6 +976,58 @@ def sample(logits, temps, top_k, top_p, uniforms, out):
     """Fused temperature / top-k / top-p sampling (GPU only; one workgroup per row)."""
     _K().sample(logits, temps, top_k, top_p, uniforms, out)
     return out
+
+
+LOGPROBS_MAX = 20   # most top log-probabilities a request may ask for (vLLM's limit)
+
+
+def sample_penalized(logits, temps, top_k, top_p, uniforms, out, state, state_rows, rep, freq, pres, min_p,
+                     full_vocab=False):
+    """``sample`` with repetition / frequency / presence penalties and min_p, into ``out`` (int32).  ``state``:
+    the [rows, V] int32 penalty-state table or None; ``state_rows[b]``: row b's state row, -1 for none.  The picked
+    tokens are counted in the state by the same call.  On the GPU one fused kernel (top_k <= 1024 candidates);
+    ``full_vocab`` (rows without such a top-k) and CPU tensors run the oracle (``reference.sample_penalized``)."""
+    if not _gpu(logits) or full_vocab:
+        out.copy_(ref.sample_penalized(logits, temps, top_k, top_p, uniforms, state, state_rows, rep, freq, pres,
+                                       min_p))
+        return out
+    _K().sample_penalized(logits.contiguous(), temps, top_k, top_p, uniforms, out, state, state_rows, rep, freq,
+                          pres, min_p)
+    return out
+
+
+def penalty_state_init(state, row, tokens, n_prompt):
+    """(Re)initialise row ``row`` of the penalty-state table in one launch: clear it, then scatter ``tokens`` (a
+    list or an int32 tensor) -- the first ``n_prompt`` are the request's prompt (flagged), the rest its sampled
+    tokens (counted).  Ids outside [0, V) are ignored."""
+    if not _gpu(state):
+        return ref.penalty_state_init(state, int(row), tokens, n_prompt)
+    if not isinstance(tokens, torch.Tensor):
+        tokens = torch.tensor(list(tokens), dtype=torch.int32)
+    _K().penalty_state_init(state, int(row), tokens.to(device=state.device, dtype=torch.int32).contiguous(),
+                            int(n_prompt))
+    return state
+
+
+def token_logprobs(logits, tokens, n, row_n=None, vals=None, ids=None):
+    """Log-softmax of the raw logits at ``tokens`` (int32 [B]) and at the ``n`` most likely tokens of each row:
+    (vals fp32 [B, 1 + n], ids int32 [B, 1 + n]), entry 0 the picked token, the rest by descending value then
+    ascending index.  ``row_n`` (int32 [B]): per-row count <= n, negative = skip the row."""
+    if not 0 <= int(n) <= LOGPROBS_MAX:
+        raise ValueError(f"token_logprobs: n={n} outside 0..{LOGPROBS_MAX}")
+    if not _gpu(logits):
+        v, i = ref.token_logprobs(logits, tokens, int(n), row_n)
+        if vals is None:
+            return v, i
+        vals.copy_(v)
+        ids.copy_(i)
+        return vals, ids
+    B = logits.shape[0]
+    if vals is None:
+        vals = torch.empty(B, 1 + int(n), dtype=torch.float32, device=logits.device)
+        ids = torch.empty(B, 1 + int(n), dtype=torch.int32, device=logits.device)
+    _K().token_logprobs(logits.contiguous(), tokens, row_n, vals, ids)
+    return vals, ids
 
 
 def rope_pairs(x, cos, sin):

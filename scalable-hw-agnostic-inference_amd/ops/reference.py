@@ -592,3 +592,125 @@ def gemm_f8(a8, w8, a_scale, w_scale, bias=None, act=None, residual=None, glu=Fa
     if residual is not None:
         y = y + res_alpha * residual.float()
     return y.to(torch.bfloat16)
+
+
+# ---------------------------------------------------------------------- sampling with penalties, min_p, logprobs
+# The oracle of csrc/kernels/sampling.hip's penalised sampler and log-probability kernel (and what the CPU engine and
+# the full-vocabulary route run).  Penalty state: one int32 word per (state row, vocabulary entry) -- bit 30: the
+# token occurs in the request's original prompt; bits 0..29: how often the sequence has sampled it.
+PENALTY_PROMPT_FLAG = 1 << 30
+PENALTY_COUNT_MASK = PENALTY_PROMPT_FLAG - 1
+
+
+def penalty_state_init(state, row, tokens, n_prompt):
+    """Clear ``state[row]`` and scatter ``tokens`` into it: the first ``n_prompt`` set the prompt flag, the rest
+    count as sampled.  Ids outside [0, V) are ignored."""
+    V = state.shape[1]
+    t = torch.as_tensor(tokens, dtype=torch.int64, device=state.device).reshape(-1)
+    n_prompt = min(int(n_prompt), t.numel())
+    ok = (t >= 0) & (t < V)
+    prompt, out = t[:n_prompt][ok[:n_prompt]], t[n_prompt:][ok[n_prompt:]]
+    words = torch.bincount(out, minlength=V).to(torch.int32)
+    flag = torch.zeros(V, dtype=torch.bool, device=state.device)
+    flag[prompt] = True
+    state[row] = words | (flag.to(torch.int32) * PENALTY_PROMPT_FLAG)
+    return state
+
+
+def penalty_state_add(state, rows, tokens):
+    """What the sampler does after picking: count token ``tokens[b]`` in state row ``rows[b]`` (rows < 0: none)."""
+    if state is None:
+        return
+    rows, tokens = rows.long(), tokens.long()
+    ok = (rows >= 0) & (rows < state.shape[0]) & (tokens >= 0) & (tokens < state.shape[1])
+    state.index_put_((rows[ok], tokens[ok]), torch.ones(int(ok.sum()), dtype=state.dtype, device=state.device),
+                     accumulate=True)
+
+
+def penalty_words(state, rows, B, V, device):
+    """The [B, V] state words of a batch (zero rows where ``rows`` < 0 or there is no table)."""
+    if state is None:
+        return torch.zeros(B, V, dtype=torch.int32, device=device)
+    ok = (rows >= 0) & (rows < state.shape[0])
+    w = state.index_select(0, rows.clamp(0, state.shape[0] - 1).long())
+    return torch.where(ok[:, None], w, torch.zeros_like(w))
+
+
+def penalize_logits(logits, words, rep, freq, pres):
+    """fp32 logits after the penalties: where the token is in the prompt or was sampled, l / rep if l > 0 else
+    l * rep (IEEE fp32 division); then l -= freq * count; then l -= pres where count > 0."""
+    l = logits.float()
+    if words is None:
+        return l
+    c = (words & PENALTY_COUNT_MASK)
+    seen = words != 0
+    r = rep.float()[:, None]
+    l = torch.where(seen, torch.where(l > 0, l / r, l * r), l)
+    l = l - freq.float()[:, None] * c.float()
+    return torch.where(c > 0, l - pres.float()[:, None], l)
+
+
+def sample_candidates(l, temps, top_k, top_p, min_p, uniforms, dtype=torch.float32, return_kept=False):
+    """The sampling rule on (already penalised) fp32 logits ``l`` [B, V]: greedy rows (temperature <= 0) take the
+    first index of the maximum; the others sort the top-k candidates (descending value, ascending index), weigh them
+    p_i = exp((l_i - l_0) / T), drop p_i < min_p (candidate 0 stays), keep candidate i of the survivors while the
+    mass before it is <= top_p of their total, and draw by inverse CDF at the uniform.  ``dtype``: precision of the
+    probabilities.  ``return_kept``: also the [B, V] mask of the tokens that can be drawn."""
+    B, V = l.shape
+    vals, idx = torch.sort(l, dim=-1, descending=True, stable=True)
+    ar = torch.arange(V, device=l.device)[None, :]
+    k = torch.where((top_k <= 0) | (top_k > V), torch.full_like(top_k, V), top_k)[:, None]
+    greedy = temps <= 0
+    T = torch.where(greedy, torch.ones_like(temps), temps).to(dtype)[:, None]
+    p = torch.exp((vals - vals[:, :1]).to(dtype) / T)
+    keep = (ar < k) & ((p >= min_p.to(dtype)[:, None]) | (ar == 0))
+    p = p * keep
+    cum = p.cumsum(-1)
+    keep = keep & ((cum - p) <= top_p.to(dtype)[:, None] * cum[:, -1:])
+    L = keep.sum(-1).clamp(min=1)
+    target = uniforms.to(dtype) * cum.gather(-1, (L - 1)[:, None]).squeeze(-1)
+    pick = ((cum <= target[:, None]) & (ar < (L - 1)[:, None])).sum(-1)
+    pick = torch.where(greedy, torch.zeros_like(pick), pick)
+    toks = idx.gather(-1, pick[:, None]).squeeze(-1)
+    if not return_kept:
+        return toks
+    keep = torch.where(greedy[:, None], ar == 0, ar < L[:, None])
+    return toks, torch.zeros(B, V, dtype=torch.bool, device=l.device).scatter_(1, idx, keep)
+
+
+def sample_penalized(logits, temps, top_k, top_p, uniforms, state=None, rows=None, rep=None, freq=None, pres=None,
+                     min_p=None, dtype=torch.float32, update=True):
+    """Penalise, sample, and count the picked tokens in ``state`` (what the fused kernel does in one launch)."""
+    B, V = logits.shape
+    words = None
+    if state is not None and rows is not None:
+        words = penalty_words(state, rows, B, V, logits.device)
+    l = penalize_logits(logits, words, rep, freq, pres)
+    if min_p is None:
+        min_p = torch.zeros(B, dtype=torch.float32, device=logits.device)
+    toks = sample_candidates(l, temps.float(), top_k.long(), top_p.float(), min_p.float(), uniforms.float(), dtype)
+    if update and state is not None and rows is not None:
+        penalty_state_add(state, rows, toks)
+    return toks
+
+
+def token_logprobs(logits, tokens, n, row_n=None, dtype=torch.float32):
+    """Log-softmax of the RAW logits at the picked token and at the ``n`` most likely tokens (descending value,
+    ascending index): (vals [B, 1 + n] fp32, ids [B, 1 + n] int32).  ``row_n``: per-row count <= n; the entries past
+    it read -inf / -1, and a row with a negative count is left at -inf / -1 altogether."""
+    B, V = logits.shape
+    lf = logits.float()
+    lp = lf.to(dtype) - torch.logsumexp(lf.to(dtype), dim=-1, keepdim=True)
+    m = min(int(n), V)
+    _, idx = torch.sort(lf, dim=-1, descending=True, stable=True)
+    idx = idx[:, :m]
+    tok = tokens.long().clamp(0, V - 1)
+    ids = torch.full((B, 1 + n), -1, dtype=torch.int64, device=logits.device)
+    vals = torch.full((B, 1 + n), float("-inf"), dtype=dtype, device=logits.device)
+    ids[:, 0], vals[:, 0] = tokens.long(), lp.gather(-1, tok[:, None]).squeeze(-1)
+    ids[:, 1:1 + m], vals[:, 1:1 + m] = idx, lp.gather(-1, idx)
+    if row_n is not None:
+        cnt = row_n.long()[:, None]
+        gone = (torch.arange(1 + n, device=logits.device)[None, :] > cnt)
+        ids, vals = ids.masked_fill(gone, -1), vals.masked_fill(gone, float("-inf"))
+    return vals.to(torch.float32 if dtype == torch.float32 else dtype), ids.to(torch.int32)

@@ -1,8 +1,11 @@
 """LLM JSON API -- compatible with app/vllm_model_api.py, app/vllm_model_api_m.py
 (multimodal ``image`` field) and app/deepseek_model_api.py.
 
-  POST /generate  {"prompt": str, "max_new_tokens": int, "image"?: base64}
-                  -> {"text": base64(utf-8 text), "execution_time": float}
+  POST /generate  {"prompt": str, "max_new_tokens": int, "image"?: base64,
+                   "temperature"?, "top_k"?, "top_p"?, "min_p"?, "repetition_penalty"?, "presence_penalty"?,
+                   "frequency_penalty"?, "seed"?, "logprobs"?: 0..20}
+                  -> {"text": base64(utf-8 text), "execution_time": float,
+                      "logprobs"?: [{"token", "logprob", "top_ids", "top_logprobs"}, ...]}   (only when asked)
   POST /benchmark {"n_runs": int, "max_new_tokens": int, "prompt": str}
                   -> {"report": base64("RESULT FOR benchmark:<app> on <nodepool> with <n> output tokens: Latency P0=...")}
   GET  /health, /readiness ("<pod> is healthy"/"... is ready"), /metrics
@@ -126,6 +129,20 @@ def create_app(service=None, env: Optional[ServerEnv] = None, tpc=None):
         max_new_tokens: int = 128
         prompt: str
         image: Optional[str] = None
+        # vLLM's request-level sampling options; an absent field keeps the server's value (SHAI_TEMPERATURE, 50,
+        # 0.9, no penalties); a value out of range is a 422
+        temperature: Optional[float] = Field(None, ge=0.0)
+        top_k: Optional[int] = None
+        top_p: Optional[float] = Field(None, gt=0.0, le=1.0)
+        min_p: Optional[float] = Field(None, ge=0.0, le=1.0)
+        repetition_penalty: Optional[float] = Field(None, gt=0.0)
+        presence_penalty: Optional[float] = Field(None, ge=-2.0, le=2.0)
+        frequency_penalty: Optional[float] = Field(None, ge=-2.0, le=2.0)
+        seed: Optional[int] = None
+        logprobs: Optional[int] = Field(None, ge=0, le=20)
+
+    SAMPLING_FIELDS = ("temperature", "top_k", "top_p", "min_p", "repetition_penalty", "presence_penalty",
+                       "frequency_penalty", "seed", "logprobs")
 
     class GenerateBenchmarkRequest(BaseModel):
         n_runs: int
@@ -135,23 +152,31 @@ def create_app(service=None, env: Optional[ServerEnv] = None, tpc=None):
     class GenerateResponse(BaseModel):
         text: str = Field(..., description="Base64-encoded text")
         execution_time: float
+        logprobs: Optional[list] = None   # one entry per generated token; present only when the request asked
 
     class GenerateBenchmarkResponse(BaseModel):
         report: str = Field(..., description="Benchmark report")
 
-    def params(n):
-        return SamplingParams(temperature=temperature, top_k=50, top_p=0.9, max_tokens=max(1, int(n)))
+    def params(n, request=None):
+        p = SamplingParams(temperature=temperature, top_k=50, top_p=0.9, max_tokens=max(1, int(n)))
+        for name in SAMPLING_FIELDS if request is not None else ():
+            v = getattr(request, name)
+            if v is not None:
+                setattr(p, name, v)
+        return p
 
     multimodal = bool(getattr(service, "multimodal", False))
 
-    def gentext(prompt: str, max_new_tokens: int, image_b64: Optional[str] = None):
+    def gentext(prompt: str, max_new_tokens: int, image_b64: Optional[str] = None, request=None):
         image = None
         if image_b64:
             image = _decode_image(image_b64)
             prompt = add_instruct(prompt, True)
             if not multimodal:
                 image = None  # text-only model: the image is validated and acknowledged, not attended to
-        text, secs, _ = service.generate_text(prompt, params(max_new_tokens), image=image)
+        text, secs, seq = service.generate_text(prompt, params(max_new_tokens, request), image=image)
+        if request is not None:
+            return text, secs, seq
         return text, secs
 
     def bench(n_runs, test_name, prompt, max_new_tokens):
@@ -179,12 +204,13 @@ def create_app(service=None, env: Optional[ServerEnv] = None, tpc=None):
             traceback.print_exc()
             raise HTTPException(status_code=500, detail=f"{e}")
 
-    @app.post("/generate", response_model=GenerateResponse)
+    @app.post("/generate", response_model=GenerateResponse, response_model_exclude_none=True)
     def generate_text_post(request: GenerateRequest):
         try:
-            text, total = gentext(request.prompt, request.max_new_tokens, request.image)
+            text, total, seq = gentext(request.prompt, request.max_new_tokens, request.image, request)
             METRICS.request_done(env, total)
-            return GenerateResponse(text=b64text(text), execution_time=total)
+            lps = list(seq.logprobs) if request.logprobs is not None else None
+            return GenerateResponse(text=b64text(text), execution_time=total, logprobs=lps)
         except Exception as e:
             traceback.print_exc()
             raise HTTPException(status_code=500, detail=f"text serialization failed: {e}")

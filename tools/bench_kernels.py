@@ -4,7 +4,8 @@
 
 python tools/bench_kernels.py [--only gemm,conv,attn,norm] [--json out.json]
 (--only kv8: decode attention over bf16 vs fp8 KV caches, then prefill attention over an fp8 cache by the native
-and the widen route; SHAI_KV8_ROWS=decode|prefill keeps one of the two groups)
+and the widen route; SHAI_KV8_ROWS=decode|prefill keeps one of the two groups;
+--only sampler: the fused sampler plain / penalised / penalised + logprobs at B = 64, alternating rounds)
 """
 import argparse
 import json
@@ -590,6 +591,50 @@ def bench_kv8_prefill(rows):
         torch.cuda.empty_cache()
 
 
+def bench_sampler(rows):
+    """Device time per call of the fused sampler at B = 64: the plain kernel, the penalised kernel (every row with a
+    state row: repetition / frequency / presence penalties and min_p) and penalised + token_logprobs (N = 5).  The
+    three variants alternate over SHAI_SAMPLER_ROUNDS (5) rounds of 32 graph-captured calls each; median, min and max
+    of the rounds are reported."""
+    import statistics
+    B, rounds = 64, int(os.environ.get("SHAI_SAMPLER_ROUNDS", "5"))
+    for V in (32000, 128256):
+        g = torch.Generator(device="cuda").manual_seed(0)
+        logits = (torch.randn(B, V, device="cuda", generator=g) * 3).to(torch.bfloat16)
+        f32 = lambda v: torch.full((B,), v, device="cuda", dtype=torch.float32)
+        temps, topp, u = f32(0.7), f32(0.9), torch.rand(B, device="cuda", generator=g)
+        topk = torch.full((B,), 50, device="cuda", dtype=torch.int32)
+        out = torch.empty(B, device="cuda", dtype=torch.int32)
+        # ~10 % of the vocabulary sampled 1..3 times, ~5 % in the prompt
+        state = (torch.randint(1, 4, (B, V), device="cuda", generator=g) *
+                 (torch.rand(B, V, device="cuda", generator=g) < 0.10)).int()
+        state |= (torch.rand(B, V, device="cuda", generator=g) < 0.05).int() << 30
+        srow = torch.arange(B, device="cuda", dtype=torch.int32)
+        rep, freq, pres, minp = f32(1.2), f32(0.3), f32(0.2), f32(0.05)
+        vals = torch.empty(B, 6, device="cuda")
+        ids = torch.empty(B, 6, device="cuda", dtype=torch.int32)
+
+        def plain():
+            ops.sample(logits, temps, topk, topp, u, out)
+
+        def pen():
+            ops.sample_penalized(logits, temps, topk, topp, u, out, state, srow, rep, freq, pres, minp)
+
+        def pen_lp():
+            pen()
+            ops.token_logprobs(logits, out, 5, None, vals, ids)
+
+        variants = {"plain": plain, "penalised": pen, "penalised+logprobs": pen_lp}
+        t = {k: [] for k in variants}
+        for _ in range(rounds):
+            for k, fn in variants.items():
+                t[k].append(graph_time(fn, iters=32, reps=1) * 1e6)
+        for k, xs in t.items():
+            rows.append({"kernel": "sampler", "variant": k, "B": B, "V": V, "us": statistics.median(xs),
+                         "us_min": min(xs), "us_max": max(xs), "x_plain": statistics.median(xs) /
+                         statistics.median(t["plain"])})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="gemm,conv,attn,norm")
@@ -600,7 +645,8 @@ def main():
         for name in a.only.split(","):
             {"gemm": bench_gemm, "conv": bench_conv, "attn": bench_attn, "norm": bench_norm,
              "decode": bench_decode, "decode_fp8": bench_decode_fp8, "fp4": bench_fp4, "sdgemm": bench_sdgemm, "f8": bench_f8,
-             "dattn": bench_dattn, "dattn_long": bench_dattn_long, "kv8": bench_kv8}[name](rows)
+             "dattn": bench_dattn, "dattn_long": bench_dattn_long, "kv8": bench_kv8,
+             "sampler": bench_sampler}[name](rows)
     for r in rows:
         print("  ".join(f"{k}={v:.1f}" if isinstance(v, float) else f"{k}={v}" for k, v in r.items()), flush=True)
     if a.json:
