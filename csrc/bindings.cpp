@@ -1549,6 +1549,58 @@ void decode_attn(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, 
   decode_attn_launch(a, k_cache, v_cache, block_table, ctx_lens, ws, num_splits, scale, k_scale, v_scale);
 }
 
+// Speculative-decoding verify attention (attention_spec.hip): q / o [B, T, Hq, D] with packed heads and a token
+// stride (o's batch stride T * token stride, q's too), bf16 cache.  ops.spec_attention sends the cases refused here
+// to the padded paged prefill kernel.
+void spec_attn(const Tensor& q, const Tensor& k_cache, const Tensor& v_cache, const Tensor& o,
+               const Tensor& block_table, const Tensor& ctx_lens, const Tensor& q_lens, const Tensor& ws,
+               int64_t num_splits, double scale) {
+  check_rows(q, "q");
+  check_rows(o, "o");
+  check_bf16(k_cache, "k_cache");
+  check_bf16(v_cache, "v_cache");
+  check_i32(block_table, "block_table");
+  check_i32(ctx_lens, "ctx_lens");
+  check_i32(q_lens, "q_lens");
+  check_f32(ws, "ws");
+  SHAI_CHECK(q.dim() == 4 && o.dim() == 4 && o.sizes() == q.sizes(), "spec_attn: q / o must be [B, T, Hq, D]");
+  SHAI_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 64 && v_cache.sizes() == k_cache.sizes() &&
+                 k_cache.is_contiguous() && v_cache.is_contiguous(), "spec_attn: caches must be contiguous [blocks, Hkv, 64, D]");
+  shai::SpecAttnArgs a{};
+  a.B = q.size(0);
+  a.T = q.size(1);
+  a.Hq = q.size(2);
+  a.D = q.size(3);
+  a.Hkv = k_cache.size(1);
+  SHAI_CHECK(a.D == 64 || a.D == 128, "spec_attn head dim 64/128");
+  SHAI_CHECK(k_cache.size(3) == a.D, "spec_attn: cache head dim != q head dim");
+  SHAI_CHECK(a.T >= 1 && a.T <= 8, "spec_attn takes 1..8 query tokens per sequence, got ", a.T);
+  SHAI_CHECK(a.Hkv > 0 && a.Hq % a.Hkv == 0, "spec_attn: Hq must be a multiple of Hkv");
+  const int G = a.Hq / a.Hkv;
+  SHAI_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "spec_attn supports GQA groups Hq / Hkv of 1, 2, 4 and 8, got ", G);
+  SHAI_CHECK(q.stride(2) == a.D && o.stride(2) == a.D, "packed heads");
+  SHAI_CHECK(a.B == 1 || a.T == 1 || (q.stride(0) == a.T * q.stride(1) && o.stride(0) == a.T * o.stride(1)),
+             "spec_attn: q / o rows must have one token stride");
+  SHAI_CHECK(block_table.dim() == 2 && block_table.size(0) == a.B && ctx_lens.numel() == a.B && q_lens.numel() == a.B,
+             "spec_attn: block_table [B, max_blocks], ctx_lens [B], q_lens [B]");
+  SHAI_CHECK(num_splits >= 1, "num_splits >= 1");
+  a.q = cptr(q);
+  a.o = mptr(o);
+  a.q_ts = a.T == 1 ? q.stride(0) : q.stride(1);
+  a.o_ts = a.T == 1 ? o.stride(0) : o.stride(1);
+  a.k_cache = cptr(k_cache);
+  a.v_cache = cptr(v_cache);
+  a.block_table = block_table.data_ptr<int>();
+  a.ctx_lens = ctx_lens.data_ptr<int>();
+  a.q_lens = q_lens.data_ptr<int>();
+  a.max_blocks = block_table.size(1);
+  a.num_splits = num_splits;
+  a.ws = ws.data_ptr<float>();
+  SHAI_CHECK(ws.numel() * 4 >= (long)shai::spec_attn_workspace(a.B, a.T, a.Hq, a.D, num_splits), "ws too small");
+  a.scale = scale;
+  shai::launch_spec_attn(a, stream());
+}
+
 // Fused decode step on the packed QKV rows [B, (h + 2 hk) D]: RoPE on q and k, this step's k / v into the paged
 // cache at slots, attention over the cached context plus the new token (replaces rope_qkv_cache +
 // decode_attn in the decode graph).
@@ -2106,6 +2158,7 @@ TORCH_LIBRARY(shai, m) {
   m.def("flash_attn(Tensor q, Tensor k, Tensor v, Tensor(a!) o, float scale, bool causal, int causal_offset, Tensor? kv_lens, Tensor? q_lens, Tensor? bias, Tensor? block_table, float k_scale=1.0, float v_scale=1.0, int q_batch_mod=0) -> ()");
   m.def("paged_attn_varlen(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor kv_lens, Tensor q_lens, Tensor q_start, int max_q, float scale, bool causal, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("decode_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor ctx_lens, Tensor(b!) ws, int num_splits, float scale, float k_scale=1.0, float v_scale=1.0) -> ()");
+  m.def("spec_attn(Tensor q, Tensor k_cache, Tensor v_cache, Tensor(a!) o, Tensor block_table, Tensor ctx_lens, Tensor q_lens, Tensor(b!) ws, int num_splits, float scale) -> ()");
   m.def("kv_write(Tensor k, Tensor v, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("kv_dequant_blocks(Tensor k_cache, Tensor v_cache, Tensor phys, Tensor(a!) k_out, Tensor(b!) v_out, float k_scale, float v_scale) -> ()");
   m.def("gated_act(Tensor x, Tensor(a!) out, int act, bool gate_first) -> ()");
@@ -2156,6 +2209,7 @@ TORCH_LIBRARY_IMPL(shai, CUDA, m) {
   m.impl("flash_attn", &flash_attn);
   m.impl("paged_attn_varlen", &paged_attn_varlen);
   m.impl("decode_attn", &decode_attn);
+  m.impl("spec_attn", &spec_attn);
   m.impl("kv_write", &kv_write);
   m.impl("kv_dequant_blocks", &kv_dequant_blocks);
   m.impl("gated_act", &gated_act);

@@ -39,7 +39,8 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 KERNEL_SRCS = ["kernels/norm.hip", "kernels/gemm.hip", "kernels/gemm_lds.hip", "kernels/gemm_8ph.hip", "kernels/gemm_w4.hip", "kernels/gemm_ws.hip", "kernels/conv_halo.hip", "kernels/attention.hip", "kernels/attention2.hip", "kernels/attention3.hip", "kernels/elementwise.hip", "kernels/dit.hip",
                "kernels/sampling.hip", "kernels/gemv.hip", "kernels/gemv2.hip", "kernels/gemv_fp4.hip",
-               "kernels/gemm_f8.hip", "kernels/attention_kv8.hip", "kernels/gemm_fp4.hip"]
+               "kernels/gemm_f8.hip", "kernels/attention_kv8.hip", "kernels/gemm_fp4.hip",
+               "kernels/attention_spec.hip"]
 # kernels that must not spill, as source -> part of the kernel's mangled name: the source is compiled with the
 # resource-usage remarks on, and build() fails when one of the named kernels reports scratch (the fp8-cache
 # instantiations of the hand-scheduled split decode kernel sit near their register budget).  The kernels are picked
@@ -50,7 +51,9 @@ NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8",
               # the fp4 tile GEMM holds up to 128 accumulators beside the widened fragments: every instantiation
               "kernels/gemm_fp4.hip": "gemm_fp4_kernel",
               # the samplers (plain and penalised) and the log-probability kernel: every instantiation
-              "kernels/sampling.hip": ("sample_kernel", "token_logprobs_kernel")}
+              "kernels/sampling.hip": ("sample_kernel", "token_logprobs_kernel"),
+              # the speculative verify attention holds the O^T accumulators of 32 query rows per wave: every form
+              "kernels/attention_spec.hip": "spec_attn_kernel"}
 NO_SCRATCH_NAMES = [p for v in NO_SCRATCH.values() for p in ((v,) if isinstance(v, str) else v)]
 # per-source extra hipcc flags: gemm_w4's epilogue (256 accumulators x an activation) is larger than LLVM's
 # default pragma-unroll budget; partially unrolled it would index the accumulators at run time (scratch)

@@ -365,6 +365,27 @@ int decode_wb_mode();
 int set_decode_wb(int mode);   // -1 keeps the mode; returns the previous one
 size_t decode_attn_workspace(int B, int Hq, int D, int num_splits);
 
+// Speculative-decoding verify attention (attention_spec.hip): T <= 8 query tokens per sequence against the paged bf16
+// cache, causal among themselves: row (b, t) sees keys j < ctx_lens[b] - q_lens[b] + t + 1.  One (sequence, KV head,
+// split) item attends all T * Hq / Hkv <= 64 rows of the KV head, so each K/V block is read once per KV head.
+// Rows t >= q_lens[b] are written as zeros.
+struct SpecAttnArgs {
+  const bf16_t* q;          // [B, T, Hq, D], token stride q_ts (heads packed)
+  const bf16_t* k_cache;    // [num_blocks, Hkv, 64, D] bf16
+  const bf16_t* v_cache;
+  bf16_t* o;                // [B, T, Hq, D], token stride o_ts
+  const int* block_table;   // [B, max_blocks]
+  const int* ctx_lens;      // [B] context length including this step's q_lens[b] tokens
+  const int* q_lens;        // [B] valid query tokens (<= T)
+  float* ws;                // split partials [B * T, Hq, num_splits, D + 2] = {m, l, o[D]}
+  int B, T, Hq, Hkv, D, max_blocks, num_splits;
+  long q_ts, o_ts;
+  float scale;
+};
+// bf16 cache, D 64 / 128, T <= 8, Hq / Hkv in {1, 2, 4, 8} (the binding checks)
+void launch_spec_attn(const SpecAttnArgs& a, hipStream_t s);
+size_t spec_attn_workspace(int B, int T, int Hq, int D, int num_splits);
+
 // Write new K/V tokens into the paged cache.
 void launch_kv_write(const bf16_t* k, const bf16_t* v, bf16_t* k_cache, bf16_t* v_cache, const int* slot_mapping,
                      int T, int Hkv, int D, long k_ts, long v_ts, hipStream_t s);

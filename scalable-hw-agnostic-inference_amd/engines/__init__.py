@@ -1,4 +1,7 @@
 """shai_amd.engines"""
+import contextlib
+import gc
+
 import torch
 
 _PRIMED: dict = {}  # device index -> the primer graph, kept alive: the generator frees its graph-safe
@@ -25,3 +28,24 @@ def new_graph(device) -> "torch.cuda.CUDAGraph":
             torch.cuda.synchronize(idx)
         _PRIMED[idx] = (g, x)
     return torch.cuda.CUDAGraph()
+
+
+@contextlib.contextmanager
+def capture(graph: "torch.cuda.CUDAGraph", **kw):
+    """``torch.cuda.graph(graph, **kw)`` with the cyclic garbage collector out of the way.
+
+    A dead Python cycle may hold device memory, pinned buffers and captured graphs: an engine and its graph
+    programs refer to each other, so a dropped engine lives until the collector finds it.  If the collector runs in
+    the middle of a capture (any allocation inside the captured program can start it) those objects are destroyed
+    there, their frees and graph destruction are calls the runtime refuses while a stream is capturing, the refusal
+    surfaces in a destructor, and the process aborts.  ``torch.cuda.graph`` no longer collects before a capture by
+    default, so: collect now, outside the capture, and keep the automatic collector off until the capture ends."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph, **kw):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from . import new_graph
+from . import capture, new_graph
 from ..models.clip import CLIPTextConfig, CLIPTextModel
 from ..models.unet2d import UNet2DConditionModel, UNetConfig
 from ..models.vae import AutoencoderKLDecoder, VAEConfig
@@ -71,7 +71,7 @@ class _UNetGraph:
             for _ in range(2):
                 self._fwd()
         torch.cuda.current_stream().wait_stream(s)
-        with torch.cuda.graph(self.graph, pool=pool):
+        with capture(self.graph, pool=pool):
             self.out = self._fwd()
 
     def _fwd(self):

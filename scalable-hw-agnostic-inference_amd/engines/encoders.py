@@ -15,6 +15,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from . import capture
 from ..tokenizers import load_tokenizer
 from ..weights import materialize
 
@@ -110,7 +111,7 @@ class ImageClassifierEngine:
                     self._forward_u8(static)
             torch.cuda.current_stream(self.device).wait_stream(side)
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with capture(graph):
                 out = self._forward_u8(static)
             g = self._graphs[B] = (graph, static, out)
         graph, static, out = g

@@ -27,7 +27,7 @@ import torch
 
 from ..utils import profiling as prof
 from .. import ops
-from . import new_graph
+from . import capture, new_graph
 from ..models.clip import CLIPTextConfig, CLIPTextModel
 from ..models.flux import FluxConfig, FluxTransformer2DModel, pack_latents, unpack_latents_nhwc
 from ..models.t5 import T5Config, T5EncoderModel
@@ -85,7 +85,7 @@ class _StepGraph:
             for _ in range(2):  # warm-up: GEMM autotuning happens here, outside capture
                 self._fwd()
         torch.cuda.current_stream().wait_stream(s)
-        with torch.cuda.graph(self.graph):
+        with capture(self.graph):
             self.out = self._fwd()
 
     def _fwd(self):

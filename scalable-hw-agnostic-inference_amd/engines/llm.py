@@ -27,6 +27,13 @@ one ``step()`` call after its token was computed; a step past a stop token is
 dropped, and steps that would pass ``max_tokens`` are never enqueued.
 With TP > 1 every rank runs the same deterministic loop (SPMD); logits are
 all-gathered so all ranks sample identically.
+With ``speculative`` (vLLM's ``speculative_config``, method ``ngram``; off by
+default) a pure decode step becomes a verify step: every sequence runs its last
+token and up to k n-gram drafts as k + 1 rows against the paged cache
+(``ops.spec_attention``), every row's next token is sampled with that
+position's noise, and the host keeps the drafts that equal what was sampled in
+front of them -- the plain engine's tokens wherever the logits agree, up to
+k + 1 of them per step.  Such an engine runs no look-ahead step.
 """
 from __future__ import annotations
 
@@ -44,7 +51,7 @@ import torch
 
 from ..utils import profiling as prof
 from .. import ops
-from . import new_graph
+from . import capture, new_graph
 from ..models.llama import (KV_BLOCK, Batch, LlamaConfig, LlamaForCausalLM, allocate_kv_cache, kv_bytes_per_block)
 from ..parallel.state import tp
 from ..weights import materialize
@@ -200,6 +207,193 @@ def sample(logits: torch.Tensor, temps: torch.Tensor, top_k: torch.Tensor, top_p
     return torch.where(temps <= 0, greedy, sampled)
 
 
+class NgramProposer:
+    """vLLM's ``method: ngram`` (prompt lookup): the draft is what followed an earlier occurrence of the sequence's
+    last tokens.  For m = ``n_max`` down to ``n_min`` the last m tokens are searched in everything before them -- the
+    earliest occurrence wins; it may overlap the suffix but is not the suffix itself -- and the first hit, at the
+    largest m, returns the up to ``k`` tokens behind it.  No hit: ``[]``.  A pure function of the token list, on the
+    host: TP ranks that mirror ``step()`` propose identically."""
+
+    def __init__(self, n_max: int = 4, n_min: int = 1):
+        self.n_max, self.n_min = int(n_max), int(n_min)
+
+    def propose(self, tokens: List[int], k: int) -> List[int]:
+        L = len(tokens)
+        if k <= 0 or L < self.n_min + 1:
+            return []
+        arr = np.asarray(tokens, dtype=np.int64)
+        for m in range(min(self.n_max, L - 1), self.n_min - 1, -1):
+            suf = arr[L - m:]
+            hit = arr[:L - m] == suf[0]                  # starts 0 .. L - m - 1: never the suffix itself
+            for j in range(1, m):
+                hit &= arr[j:L - m + j] == suf[j]
+            at = np.flatnonzero(hit)
+            if at.size:
+                i = int(at[0]) + m
+                return [int(t) for t in arr[i:i + k]]
+        return []
+
+
+def parse_speculative(spec: Optional[dict]) -> Optional[dict]:
+    """Validate a vLLM-style ``speculative_config`` ({"method": "ngram", "num_speculative_tokens": k,
+    "prompt_lookup_max": N = 4, "prompt_lookup_min": n = 1}); returns the normalised dict, None for None."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError(f"speculative must be a dict of vLLM's speculative_config keys, got {spec!r}")
+    known = {"method", "num_speculative_tokens", "prompt_lookup_max", "prompt_lookup_min"}
+    if set(spec) - known:
+        raise ValueError(f"speculative: unknown keys {sorted(set(spec) - known)}; supported: {sorted(known)}")
+    method = spec.get("method", "ngram")
+    if method != "ngram":
+        raise ValueError(f"speculative method {method!r}: only 'ngram' (prompt lookup) is supported")
+    integer = lambda x: isinstance(x, numbers.Integral) and not isinstance(x, bool)
+    k, N, n = spec.get("num_speculative_tokens"), spec.get("prompt_lookup_max", 4), spec.get("prompt_lookup_min", 1)
+    if not (integer(k) and 1 <= k <= ops.SPEC_MAX_T - 1):
+        raise ValueError(f"num_speculative_tokens must be an integer in 1..{ops.SPEC_MAX_T - 1}, got {k!r}")
+    if not (integer(N) and integer(n) and 1 <= n <= N):
+        raise ValueError(f"prompt_lookup_min / prompt_lookup_max must be integers with 1 <= min <= max, got {n!r}, "
+                         f"{N!r}")
+    return {"method": "ngram", "num_speculative_tokens": int(k), "prompt_lookup_max": int(N),
+            "prompt_lookup_min": int(n)}
+
+
+def accept_drafts(sampled: Sequence[int], draft: Sequence[int]) -> List[int]:
+    """The tokens one verify step emits for a sequence: ``sampled[t]`` is the token drawn behind row t (row 0 the
+    sequence's last token, row t > 0 draft t - 1).  ``sampled[0]`` always; while ``sampled[t] == draft[t]`` the draft
+    was the token the model draws there, so the next row's context was right and ``sampled[t + 1]`` follows.  With a
+    one-hot proposal this is exact rejection sampling: a draft is accepted with probability p(draft), and what is
+    drawn otherwise is distributed as p without the draft, renormalised."""
+    out = [int(sampled[0])]
+    for t, d in enumerate(draft):
+        if int(sampled[t]) != int(d):
+            break
+        out.append(int(sampled[t + 1]))
+    return out
+
+
+class _SpecGraph:
+    """One verify step of speculative decoding for batch bucket ``Bc`` and ``T`` = 1 + k rows per sequence as a single
+    captured program: model forward on the [Bc, T] rows -> sampling of every row.  As in :class:`_DecodeGraph` all
+    per-step inputs live in one int32 device buffer filled by one pinned copy; the [Bc, T] sampled tokens come back in
+    one copy.  No token feedback: the number of tokens a step emits is only known after read-back."""
+
+    NR = 7   # per-row int32 fields: ids, positions, slots, top_k, temperature, top_p, uniform
+    NS = 2   # per-sequence: context length, valid rows
+
+    def __init__(self, engine: "LLMEngine", Bc: int, T: int, greedy: bool, splits: int):
+        self.engine, self.Bc, self.T, self.greedy, self.splits = engine, Bc, T, greedy, splits
+        dev, mb, R = engine.device, engine.max_blocks, Bc * T
+        self.words = self.NR * R + self.NS * Bc + Bc * mb
+        self.dbuf = torch.zeros(self.words, dtype=torch.int32, device=dev)
+        f = lambda i: self.dbuf[i * R:(i + 1) * R]
+        self.ids, self.pos, self.slots, self.topk = f(0), f(1), f(2), f(3)
+        self.temps, self.topp, self.u = f(4).view(torch.float32), f(5).view(torch.float32), f(6).view(torch.float32)
+        o = self.NR * R
+        self.lens, self.qlens = self.dbuf[o:o + Bc], self.dbuf[o + Bc:o + 2 * Bc]
+        self.bt = self.dbuf[o + 2 * Bc:].view(Bc, mb)
+        self.slots.fill_(-1)
+        self.lens.fill_(1)
+        self.qlens.fill_(1)
+        self.topk.fill_(1)
+        self.topp.fill_(1.0)
+        self.toks = torch.zeros(R, dtype=torch.int32, device=dev)
+        pin = dev.type == "cuda"
+        self.host = [torch.zeros(self.words, dtype=torch.int32, pin_memory=pin) for _ in range(2)]
+        self.host_np = [h.numpy() for h in self.host]
+        self.host_ev = [None, None]
+        self.out_host = torch.zeros(R, dtype=torch.int32, pin_memory=pin)
+        self.flip = 0
+        self.batch = Batch(self.ids, self.pos, self.slots, self.bt, self.lens, self.qlens, Bc, T, False, splits,
+                           spec_T=T)
+        self.graph = None
+        if engine.use_graphs:   # (the warm-up forwards use padding rows only: no KV-cache row is written)
+            st = torch.cuda.Stream()
+            st.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st):
+                for _ in range(2):
+                    self._program()
+            torch.cuda.current_stream().wait_stream(st)
+            self.graph = new_graph(dev)
+            with capture(self.graph):
+                self._program()
+
+    def _program(self):
+        eng = self.engine
+        logits = eng.model(self.batch, eng.kv)
+        if self.greedy:
+            self.toks.copy_(logits.float().argmax(-1))
+        elif logits.is_cuda:
+            sample(logits, self.temps, self.topk, self.topp, uniforms=self.u, out=self.toks, full_vocab=False)
+        else:
+            self.toks.copy_(sample(logits, self.temps, self.topk, self.topp, uniforms=self.u))
+
+    def launch(self, seqs, drafts) -> np.ndarray:
+        """Run one verify step of ``seqs`` (``drafts[b]``: sequence b's draft tokens, already cut to what fits) and
+        return the sampled tokens [B, T] on the host."""
+        B, Bc, T, R = len(seqs), self.Bc, self.T, self.Bc * self.T
+        i = self.flip
+        self.flip ^= 1
+        if self.host_ev[i] is not None:
+            self.host_ev[i].synchronize()
+        h = self.host_np[i]
+        v = lambda k: h[k * R:(k + 1) * R].reshape(Bc, T)
+        ids, pos, slots, topk = v(0), v(1), v(2), v(3)
+        temps, topp, u = v(4).view(np.float32), v(5).view(np.float32), v(6).view(np.float32)
+        o = self.NR * R
+        lens, qlens = h[o:o + Bc], h[o + Bc:o + 2 * Bc]
+        btv = h[o + 2 * Bc:].reshape(Bc, -1)
+        # padding rows and sequences: token 0 at position 0, no KV write, greedy; a one-token context of block 0
+        ids[:] = 0
+        pos[:] = 0
+        slots[:] = -1
+        topk[:] = 1
+        temps[:] = 0.0
+        topp[:] = 1.0
+        u[:] = 0.0
+        lens[:] = 1
+        qlens[:] = 1
+        btv[:] = 0
+        keys, upos = [], []
+        for b, (s, d) in enumerate(zip(seqs, drafts)):
+            n = 1 + len(d)
+            p0 = s.length - 1
+            ids[b, :n] = [s.last_token] + list(d)
+            pp = np.arange(p0, p0 + n)
+            pos[b, :n] = pp
+            blocks = np.asarray(s.blocks, dtype=np.int64)
+            slots[b, :n] = blocks[pp // KV_BLOCK] * KV_BLOCK + pp % KV_BLOCK
+            topk[b, :n] = s.params.top_k
+            temps[b, :n] = s.params.temperature
+            topp[b, :n] = s.params.top_p
+            lens[b] = p0 + n
+            qlens[b] = n
+            btv[b, :len(s.blocks)] = s.blocks
+            keys += [s.rng_key] * n
+            upos += [s.length + t for t in range(n)]     # row t samples the token at absolute position length + t
+        if not self.greedy:
+            uu = seq_uniforms(keys, upos)
+            k0 = 0
+            for b, d in enumerate(drafts):
+                u[b, :1 + len(d)] = uu[k0:k0 + 1 + len(d)]
+                k0 += 1 + len(d)
+        self.dbuf.copy_(self.host[i], non_blocking=True)
+        if self.dbuf.is_cuda:
+            ev = torch.cuda.Event()
+            ev.record()
+            self.host_ev[i] = ev
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._program()
+        self.out_host.copy_(self.toks, non_blocking=True)
+        if self.dbuf.is_cuda:
+            done = torch.cuda.Event()
+            done.record()
+            done.synchronize()
+        return self.out_host.numpy().reshape(Bc, T)[:B].copy()
+
+
 class _DecodeGraph:
     """One decode step for batch bucket ``Bc`` as a single captured program (HIP graph on the GPU):
     token feedback -> model forward -> sampling -> publish tokens.
@@ -278,7 +472,7 @@ class _DecodeGraph:
                     self._program()
             torch.cuda.current_stream().wait_stream(s)
             self.graph = new_graph(dev)
-            with torch.cuda.graph(self.graph):
+            with capture(self.graph):
                 self._program()
             engine.last_tokens.copy_(saved)
 
@@ -432,8 +626,10 @@ class LLMEngine:
                  quantization: Optional[str] = None, async_decode: Optional[bool] = None,
                  packed_prefill: bool = True, mixed_steps: bool = True, kv_cache_dtype: Optional[str] = None,
                  k_scale: float = 1.0, v_scale: float = 1.0, kv_scratch_blocks: Optional[int] = None,
-                 kv_prefill: Optional[str] = None):
+                 kv_prefill: Optional[str] = None, speculative: Optional[dict] = None):
         from ..models.mllama import MllamaConfig, MllamaForConditionalGeneration
+        # speculative decoding (vLLM's speculative_config, method ngram): None = off, the engine as it always was
+        self.speculative = parse_speculative(speculative)
         from ..runtime import BlockManager
         self.kv_cache_dtype, self.kv_dtype = resolve_kv_cache_dtype(kv_cache_dtype)
         self.kv_fp8 = self.kv_dtype == torch.float8_e4m3fn
@@ -447,6 +643,9 @@ class LLMEngine:
         if self.kv_fp8 and self.mcfg is not None:
             raise NotImplementedError("kv_cache_dtype=fp8 is not supported yet for multimodal (mllama) models: the "
                                       "image cross-attention K/V path is bf16 only")
+        if self.speculative is not None and self.mcfg is not None:
+            raise NotImplementedError("speculative decoding is not supported yet for multimodal (mllama) models: the "
+                                      "verify step has no image cross-attention path")
         if self.kv_fp8 and not (k_scale > 0 and v_scale > 0 and math.isfinite(k_scale) and math.isfinite(v_scale)):
             raise ValueError(f"k_scale / v_scale must be positive and finite, got {k_scale}, {v_scale}")
         if self.mcfg is not None:
@@ -533,6 +732,13 @@ class LLMEngine:
         if async_decode is None:
             async_decode = os.environ.get("SHAI_ASYNC_DECODE", "1") != "0"
         self.async_decode = bool(async_decode)
+        self.proposer = None
+        self.spec_k = 0
+        if self.speculative is not None:
+            # the number of tokens a verify step emits is not known before read-back: no look-ahead step
+            self.async_decode = False
+            self.spec_k = self.speculative["num_speculative_tokens"]
+            self.proposer = NgramProposer(self.speculative["prompt_lookup_max"], self.speculative["prompt_lookup_min"])
         self._inflight: Optional[_Inflight] = None
         bmax = 1 << max(0, math.ceil(math.log2(max(1, max_num_seqs))))
         self.last_tokens = torch.zeros(bmax, dtype=torch.int32, device=self.device)
@@ -546,6 +752,8 @@ class LLMEngine:
         self._pen_free: List[int] = list(range(max_num_seqs - 1, -1, -1))
         self._lp_host: Optional[List[torch.Tensor]] = None
         self.stats = {"prefill_tokens": 0, "decode_tokens": 0, "steps": 0, "prefix_hit_tokens": 0}
+        if self.speculative is not None:   # verify steps run, draft tokens proposed, draft tokens accepted
+            self.stats.update(spec_steps=0, spec_drafted=0, spec_accepted=0)
         self.eos = {cfg.eos_token_id}
 
     def set_kv_scales(self, k_scales: Sequence[float], v_scales: Sequence[float]) -> None:
@@ -874,6 +1082,76 @@ class LLMEngine:
             return None
         return self._launch(seqs, [s.length - 1 for s in seqs], [s.last_token for s in seqs], [-1] * len(seqs))
 
+    def _spec_ok(self, seqs) -> bool:
+        """Whether a pure decode step of ``seqs`` may run as a verify step: speculation is on and no sequence needs a
+        penalty-state row, min_p, logprobs or the full-vocabulary sampler (those steps take the plain path)."""
+        if self.proposer is None:
+            return False
+        for s in seqs:
+            p = s.params
+            if s.pen_row >= 0 or p.penalised or p.min_p > 0 or p.logprobs is not None:
+                return False
+            if p.temperature > 0 and not 0 < p.top_k <= ops.SAMPLER_MAX_K:
+                return False
+        return True
+
+    def _spec_decode(self, seqs: List[Sequence_]) -> None:
+        """One verify step: sequence b runs its last token and d_b <= k draft tokens as T_b = 1 + d_b rows, every
+        row's next token is sampled (noise of row t: ``seq_uniforms(key, length + t)``, the plain path's value for
+        that position), and the host accepts drafts while they equal what was sampled in front of them
+        (:func:`accept_drafts`).  Every emitted token goes through ``_append`` in order; a stop token or a length
+        limit inside an accepted run drops the rest.  A rejected draft's K / V slot is rewritten by a later step
+        before any row may see it (contexts end at the last emitted token)."""
+        seqs = self._preempt_short(seqs)
+        if not seqs:
+            return
+        k, V = self.spec_k, self.cfg.vocab_size
+        drafts = []
+        for s in seqs:
+            room = min(k, s.params.max_tokens - len(s.output) - 1, self.max_model_len - s.length - 1)
+            d = [int(t) for t in self.proposer.propose(s.tokens, k)][:max(room, 0)] if room > 0 else []
+            for j, t in enumerate(d):        # a proposer's out-of-vocabulary token ends its draft
+                if not 0 <= t < V:
+                    d = d[:j]
+                    break
+            while d and not self._ensure_blocks(s, s.length + len(d)):   # cut the drafts rather than preempt
+                d.pop()
+            drafts.append(d)
+        B, T = len(seqs), k + 1
+        Bc = 1 << max(0, math.ceil(math.log2(B)))
+        greedy = all(s.params.temperature <= 0 for s in seqs)
+        splits = self.decode_splits(Bc, max(s.length + len(d) for s, d in zip(seqs, drafts)))
+        key = ("spec", Bc, T, greedy, splits)
+        g = self._graphs.get(key)
+        if g is None:
+            g = self._graphs[key] = _SpecGraph(self, Bc, T, greedy, splits)
+        sampled = g.launch(seqs, drafts)
+        self.stats["spec_steps"] += 1
+        self.stats["decode_tokens"] += B
+        for b, (s, d) in enumerate(zip(seqs, drafts)):
+            self.stats["spec_drafted"] += len(d)
+            for j, tok in enumerate(accept_drafts(sampled[b], d)):
+                self._append([s], [tok])
+                self.stats["spec_accepted"] += 1 if j else 0
+                if s.finished:
+                    break
+            s.n_cached = s.length - 1
+
+    def _preempt_short(self, seqs: List[Sequence_]) -> List[Sequence_]:
+        """Preempt (recompute later) the sequences of a decode step that get no block for their next token; returns
+        the ones that stay."""
+        for s in seqs:
+            if not self._ensure_blocks(s, s.length):
+                self._free(s)
+                s.n_cached = 0
+                s.prefill_started = False
+                s.prompt = s.prompt + s.output
+                s.output = []
+                self.running.remove(s)
+                self.waiting.insert(0, s)
+        running = set(map(id, self.running))
+        return [s for s in seqs if id(s) in running]
+
     def _launch(self, seqs, ctx_before, ids, rowmap) -> _Inflight:
         from ..runtime import build_decode
         B = len(seqs)
@@ -1045,6 +1323,10 @@ class LLMEngine:
             with prof.range_("llm_prefill"):
                 self._prefill(pending + adm, decodable if mix else ())
             self._last_step = "prefill"
+        elif decodable and self._spec_ok(self.running):
+            with prof.range_("llm_spec_decode"):
+                self._spec_decode(decodable)
+            self._last_step = "decode"
         elif decodable:
             with prof.range_("llm_decode"):
                 h = self._decode(decodable)

@@ -168,6 +168,10 @@ class Batch:
     # native route, packed steps: launch groups (first sequence, count, largest q_len) -- the prefill chunks, then
     # the decode rows that joined the step (see ops.paged_attention_varlen); None = one launch
     q_groups: Optional[list] = None
+    # speculative verify step (not a prefill step): the rows are [B, spec_T] at a fixed stride -- each sequence's last
+    # token and its drafts, padding rows with slot -1 -- q_lens holds the valid rows per sequence, ctx_lens count them,
+    # and the forward returns logits for all B * spec_T rows.  0 = any other step.
+    spec_T: int = 0
 
 
 class LlamaAttention(nn.Module):
@@ -192,6 +196,13 @@ class LlamaAttention(nn.Module):
         h, hk, hd = self.h, self.hk, self.hd
         ks, vs = self.k_scale, self.v_scale
         qp = self.qkv_proj
+        if batch.spec_T > 0:   # verify step: T rows per sequence against the cache that rope_qkv_cache just extended
+            qkv = qp(x, rms_eps=rms_eps)
+            ops.rope_qkv_cache(qkv, batch.positions, cos, sin, k_cache, v_cache, batch.slots, h, hk, ks, vs)
+            q = qkv[:, : h * hd].view(batch.B, batch.spec_T, h, hd)
+            o = ops.spec_attention(q, k_cache, v_cache, batch.block_table, batch.ctx_lens, batch.q_lens, self.scale,
+                                   num_splits=batch.num_splits, k_scale=ks, v_scale=vs).reshape(T, h * hd)
+            return self.o_proj(o, residual=residual)
         if (not batch.is_prefill and FUSED_DECODE and QKV_FOLD_IN_ATTN and rms_eps is not None and x.is_cuda
                 and (batch.num_splits or 1) <= QKV_FOLD_MAX_SPLITS and T <= 64 and qp.bias is None and qp.w_scale is None and qp.weight.dtype == torch.bfloat16
                 and x.is_contiguous() and x.shape[1] >= 2048):
@@ -296,7 +307,8 @@ class LlamaForCausalLM(nn.Module):
         return self._rope
 
     def forward(self, batch: Batch, kv_caches: List[tuple]) -> torch.Tensor:
-        """Returns logits [B, V] for each sequence's last token of this step."""
+        """Returns logits [B, V] for each sequence's last token of this step (a verify step, ``batch.spec_T`` > 0:
+        [B * spec_T, V], every row's)."""
         if not self._folded:
             self.fold_norms()
         cos, sin = self.rope(batch.input_ids.device)

@@ -877,6 +877,49 @@ def decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale=None, num
     return o
 
 
+SPEC_MAX_T = 8   # query tokens per sequence the verify kernel takes (1 + up to 7 drafts)
+
+
+def spec_attention_native(q, k_cache, v_cache) -> bool:
+    """Whether :func:`spec_attention` runs csrc/kernels/attention_spec.hip for these operands (GPU, bf16 cache,
+    D 64 / 128, T <= 8, Hq / Hkv in {1, 2, 4, 8}); everything else takes the padded paged prefill kernel."""
+    if not _gpu(q) or _kv8(k_cache, v_cache) or os.environ.get("SHAI_SPEC_ATTN", "1") == "0":
+        return False
+    _, T, Hq, D = q.shape
+    Hkv = k_cache.shape[1]
+    return D in (64, 128) and T <= SPEC_MAX_T and Hq % Hkv == 0 and Hq // Hkv in (1, 2, 4, 8)
+
+
+def spec_attention(q, k_cache, v_cache, block_table, ctx_lens, q_lens, scale=None, num_splits: Optional[int] = None,
+                   out=None, k_scale: float = 1.0, v_scale: float = 1.0):
+    """Verify attention of speculative decoding: q [B, T, Hq, D] holds each sequence's last token and its drafts,
+    whose K / V are already in the paged cache; ``ctx_lens`` count them.  Row (b, t) sees the keys
+    j < ctx_lens[b] - q_lens[b] + t + 1; rows t >= q_lens[b] are unspecified.  The split kernel of
+    attention_spec.hip reads each K / V block once per KV head for all T * Hq / Hkv rows; unsupported cases
+    (:func:`spec_attention_native`) run the padded :func:`paged_attention` (an fp8 cache its native route), the CPU
+    ``ref.paged_attention``."""
+    D = q.shape[-1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    if not _gpu(q):
+        o = ref.paged_attention(q, k_cache, v_cache, block_table, ctx_lens, q_lens, scale, True, k_scale, v_scale)
+    elif spec_attention_native(q, k_cache, v_cache):
+        B, T, Hq, _ = q.shape
+        if num_splits is None:
+            num_splits = decode_splits(B, k_cache.shape[1], block_table.shape[1] * 64)
+        ws = torch.empty(B * T * Hq * num_splits * (D + 2), dtype=torch.float32, device=q.device)
+        o = out if out is not None else torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        _K().spec_attn(q, k_cache, v_cache, o, _i32(block_table), _i32(ctx_lens), _i32(q_lens), ws, int(num_splits),
+                       float(scale))
+        return o
+    else:
+        o = paged_attention(q, k_cache, v_cache, block_table, ctx_lens, q_lens, scale, causal=True, k_scale=k_scale,
+                            v_scale=v_scale, kv_prefill="native")
+    if out is not None:
+        out.copy_(o)
+        return out
+    return o
+
+
 def decode_attention_rope(qkv, k_cache, v_cache, block_table, ctx_lens, positions, cos, sin, slots, h: int, hk: int,
                           scale=None, num_splits: Optional[int] = None, max_ctx: Optional[int] = None, out=None,
                           k_scale: float = 1.0, v_scale: float = 1.0):

@@ -24,7 +24,11 @@ cache with scalar k/v scales -- half the KV bytes per decode step, twice the
 tokens per block pool; every TP rank reads the same file, so the relaunched
 ranks build the same cache) with kv_prefill (``widen``, the default, or
 ``native``: the prefill attention reads the fp8 cache directly and the engine
-holds no bf16 scratch).
+holds no bf16 scratch) and speculative_config (vLLM's keys: ``method: ngram``,
+``num_speculative_tokens`` 1..7, ``prompt_lookup_max`` 4, ``prompt_lookup_min``
+1: pure decode steps verify n-gram drafts from the sequence's own tokens, up to
+1 + k tokens per sequence and step; the responses do not change.  Off when
+absent; text models only).
 
 Tensor parallelism (``tensor_parallel_size: N``, app/vllm_model_api.py:127-129 with
 cova/mllama-32-11b-vllm-trn1-config.yaml:9): the worker runs as N processes, one
@@ -76,7 +80,8 @@ def build_engine(env: ServerEnv, vc: Optional[dict] = None):
                     max_num_seqs=int(vc.get("max_num_seqs", 64)),
                     max_model_len=int(vc.get("max_model_len", min(8192, text.max_position_embeddings))),
                     enable_prefix_caching=True, quantization=vc.get("quantization"),
-                    kv_cache_dtype=vc.get("kv_cache_dtype"), kv_prefill=vc.get("kv_prefill"))
+                    kv_cache_dtype=vc.get("kv_cache_dtype"), kv_prefill=vc.get("kv_prefill"),
+                    speculative=vc.get("speculative_config"))
     import torch
     with torch.inference_mode():
         # every decode batch bucket (sampled and all-greedy) captured before the first request
