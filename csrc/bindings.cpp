@@ -1715,8 +1715,14 @@ void kv_write(const Tensor& k, const Tensor& v, const Tensor& k_cache, const Ten
   }
   check_bf16(k_cache, "k_cache");
   check_bf16(v_cache, "v_cache");
-  SHAI_CHECK(k.dim() == 3 && k_cache.dim() == 4, "k [T, Hkv, D], cache [blocks, Hkv, 64, D]");
+  SHAI_CHECK(k.dim() == 3 && k_cache.dim() == 4 && k_cache.size(2) == 64 && v_cache.sizes() == k_cache.sizes() &&
+                 k_cache.is_contiguous() && v_cache.is_contiguous(),
+             "k [T, Hkv, D], caches contiguous [blocks, Hkv, 64, D]");
+  SHAI_CHECK(v.sizes() == k.sizes() && k.size(1) == k_cache.size(1) && k.size(2) == k_cache.size(3),
+             "k / v [T, Hkv, D] must match the cache [blocks, Hkv, 64, D]");
+  SHAI_CHECK(k.size(2) % 8 == 0, "kv_write needs D % 8 == 0, got D = ", k.size(2));
   SHAI_CHECK(k.stride(1) == k.size(2) && v.stride(1) == v.size(2), "packed heads");
+  SHAI_CHECK(slots.numel() == k.size(0), "slots must have T entries");
   shai::launch_kv_write(cptr(k), cptr(v), mptr(k_cache), mptr(v_cache), slots.data_ptr<int>(), k.size(0), k.size(1),
                         k.size(2), k.stride(0), v.stride(0), stream());
 }
@@ -1750,7 +1756,15 @@ void bias_act(const Tensor& x, const optional<Tensor>& bias, const optional<Tens
   SHAI_CHECK(x.is_contiguous() && out.is_contiguous(), "bias_act contiguous");
   const int D = x.size(-1);
   SHAI_CHECK(D % 8 == 0, "D % 8");
-  if (residual) SHAI_CHECK(residual->is_contiguous() && residual->numel() == x.numel(), "residual");
+  SHAI_CHECK(out.numel() == x.numel(), "bias_act: out must have x's size");
+  if (bias) {
+    check_bf16(*bias, "bias");
+    SHAI_CHECK(bias->numel() == D, "bias_act: bias must have D = ", D, " elements, got ", bias->numel());
+  }
+  if (residual) {
+    check_bf16(*residual, "residual");
+    SHAI_CHECK(residual->is_contiguous() && residual->numel() == x.numel(), "residual");
+  }
   shai::launch_bias_act(cptr(x), optr(bias), optr(residual), mptr(out), x.numel() / D, D, act, alpha, stream());
 }
 
@@ -1760,6 +1774,12 @@ void rope(const Tensor& x, const Tensor& positions, const Tensor& cos, const Ten
   check_f32(cos, "cos");
   check_f32(sin, "sin");
   SHAI_CHECK(x.dim() == 3 && x.stride(1) == x.size(2), "rope x must be [T, H, Dh] with packed heads");
+  const int64_t Dh = x.size(2);
+  SHAI_CHECK(rot_dim > 0 && rot_dim % 2 == 0 && rot_dim <= Dh, "rope: rot_dim must be even and in (0, Dh = ", Dh,
+             "], got ", rot_dim);
+  SHAI_CHECK(cos.dim() == 2 && cos.size(1) == rot_dim / 2 && sin.sizes() == cos.sizes(),
+             "rope: cos / sin must be [max_pos, rot_dim / 2 = ", rot_dim / 2, "]");
+  SHAI_CHECK(positions.numel() == x.size(0), "rope: positions must have T entries");
   shai::launch_rope(mptr(x), positions.data_ptr<int>(), cos.data_ptr<float>(), sin.data_ptr<float>(), x.size(0),
                     x.size(1), x.size(2), rot_dim, x.stride(0), neox, stream());
 }
@@ -1911,7 +1931,9 @@ void rope_pairs(const Tensor& x, const Tensor& cos, const Tensor& sin) {
   check_f32(cos, "cos");
   check_f32(sin, "sin");
   SHAI_CHECK(x.dim() == 4 && x.stride(2) == x.size(3) && x.size(3) % 8 == 0, "rope_pairs x [B, T, H, Dh]");
-  SHAI_CHECK(cos.numel() == x.size(1) * x.size(3) / 2, "cos/sin must be [T, Dh/2]");
+  SHAI_CHECK(cos.numel() == x.size(1) * x.size(3) / 2 && sin.numel() == cos.numel(), "cos/sin must be [T, Dh/2]");
+  SHAI_CHECK((x.stride(0) % 8 == 0 || x.size(0) == 1) && (x.stride(1) % 8 == 0 || x.size(1) == 1),
+             "rope_pairs: batch and token strides must be 16-byte aligned");
   shai::launch_rope_pairs(mptr(x), cos.data_ptr<float>(), sin.data_ptr<float>(), x.size(0), x.size(1), x.size(2),
                           x.size(3), x.stride(0), x.stride(1), stream());
 }
@@ -1990,7 +2012,10 @@ void embedding(const Tensor& ids, const Tensor& table, const Tensor& out) {
   check_i32(ids, "ids");
   check_bf16(table, "table");
   check_bf16(out, "out");
-  SHAI_CHECK(table.is_contiguous() && out.is_contiguous() && table.size(1) % 8 == 0, "embedding shapes");
+  SHAI_CHECK(table.dim() == 2 && table.is_contiguous() && out.is_contiguous() && table.size(1) % 8 == 0,
+             "embedding shapes");
+  SHAI_CHECK(out.dim() >= 1 && out.size(-1) == table.size(1) && out.numel() == ids.numel() * table.size(1),
+             "embedding: out must be [ids..., D]");
   shai::launch_embedding(ids.data_ptr<int>(), cptr(table), mptr(out), ids.numel(), table.size(1), stream());
 }
 

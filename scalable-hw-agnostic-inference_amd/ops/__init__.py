@@ -1004,7 +1004,7 @@ def rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, heads: int
     D = k_cache.shape[-1]
     if not _gpu(qkv):
         q = qkv[:, : heads * D].view(T, heads, D)
-        k = qkv[:, heads * D:(heads + kv_heads) * D].view(T, kv_heads, D)
+        k = qkv[:, heads * D:(heads + kv_heads) * D].view(T, kv_heads, D).clone()   # as the kernel: k in qkv stays
         v = qkv[:, (heads + kv_heads) * D:].view(T, kv_heads, D)
         ref.rope(q, positions, cos, sin, D, True)
         ref.rope(k, positions, cos, sin, D, True)

@@ -41,9 +41,10 @@ def apply_act(x: torch.Tensor, act) -> torch.Tensor:
 
 def rmsnorm(x, w, eps, residual=None, w_offset=0.0):
     xf = x.float()
-    if residual is not None:
-        xf = xf + residual.float()
-    new_res = xf.to(x.dtype) if residual is not None else None
+    new_res = None
+    if residual is not None:   # the kernels normalise the rounded sum they also return (as Hugging Face and vLLM do)
+        new_res = (xf + residual.float()).to(x.dtype)
+        xf = new_res.float()
     y = xf * torch.rsqrt(xf.pow(2).mean(-1, keepdim=True) + eps)
     if w is not None:
         y = y * (w.float() + w_offset)
@@ -52,9 +53,10 @@ def rmsnorm(x, w, eps, residual=None, w_offset=0.0):
 
 def layernorm(x, w, b, eps, residual=None):
     xf = x.float()
-    if residual is not None:
-        xf = xf + residual.float()
-    new_res = xf.to(x.dtype) if residual is not None else None
+    new_res = None
+    if residual is not None:   # the kernels normalise the rounded sum they also return (as Hugging Face and vLLM do)
+        new_res = (xf + residual.float()).to(x.dtype)
+        xf = new_res.float()
     y = F.layer_norm(xf, (x.shape[-1],), w.float() if w is not None else None, b.float() if b is not None else None,
                      eps)
     return y.to(x.dtype), new_res
