@@ -1893,6 +1893,65 @@ void sample_penalized(const Tensor& logits, const Tensor& temps, const Tensor& t
                                 freq.data_ptr<float>(), pres.data_ptr<float>(), min_p.data_ptr<float>(), stream());
 }
 
+// the fused sampler with constraint programs on top of the penalties (launch_sample_constrained): pool int32 [P]
+// (programs back to back), cstate int32 [slots], per row program offset / state slot / ban-stop flag
+void sample_constrained(const Tensor& logits, const Tensor& temps, const Tensor& top_k, const Tensor& top_p,
+                        const Tensor& uniforms, const Tensor& out, const optional<Tensor>& state,
+                        const Tensor& state_rows, const Tensor& rep, const Tensor& freq, const Tensor& pres,
+                        const Tensor& min_p, const Tensor& pool, const Tensor& cstate, const Tensor& prog,
+                        const Tensor& slot, const Tensor& ban) {
+  SHAI_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be a 2D GPU tensor");
+  const bool bf16 = logits.scalar_type() == at::kBFloat16;
+  SHAI_CHECK(bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or fp32");
+  const int B = logits.size(0);
+  const long V = logits.size(1);
+  check_f32(temps, "temps");
+  check_f32(top_p, "top_p");
+  check_f32(uniforms, "uniforms");
+  check_i32(top_k, "top_k");
+  check_i32(out, "out");
+  check_i32(state_rows, "state_rows");
+  check_f32(rep, "repetition_penalty");
+  check_f32(freq, "frequency_penalty");
+  check_f32(pres, "presence_penalty");
+  check_f32(min_p, "min_p");
+  check_i32(pool, "constraint pool");
+  check_i32(cstate, "constraint state");
+  check_i32(prog, "program offsets");
+  check_i32(slot, "state slots");
+  check_i32(ban, "ban_stop");
+  SHAI_CHECK(temps.numel() == B && top_p.numel() == B && uniforms.numel() == B && top_k.numel() == B &&
+                 out.numel() == B && state_rows.numel() == B && rep.numel() == B && freq.numel() == B &&
+                 pres.numel() == B && min_p.numel() == B && prog.numel() == B && slot.numel() == B &&
+                 ban.numel() == B,
+             "per-row parameter sizes");
+  SHAI_CHECK(pool.dim() == 1 && cstate.dim() == 1 && cstate.numel() < (1L << 31),
+             "constraint pool and state must be 1-D int32");
+  int* st = nullptr;
+  int n_rows = 0;
+  if (state.has_value()) {
+    check_i32(*state, "state");
+    SHAI_CHECK(state->dim() == 2 && state->size(1) == V, "penalty state must be [rows, V] int32 with the logits' V");
+    st = state->data_ptr<int>();
+    n_rows = state->size(0);
+  }
+  shai::launch_sample_constrained(logits.data_ptr(), bf16, logits.stride(0), B, V, temps.data_ptr<float>(),
+                                  top_k.data_ptr<int>(), top_p.data_ptr<float>(), uniforms.data_ptr<float>(),
+                                  out.data_ptr<int>(), st, n_rows, state_rows.data_ptr<int>(), rep.data_ptr<float>(),
+                                  freq.data_ptr<float>(), pres.data_ptr<float>(), min_p.data_ptr<float>(),
+                                  pool.numel() ? pool.data_ptr<int>() : nullptr, pool.numel(),
+                                  cstate.numel() ? cstate.data_ptr<int>() : nullptr, (int)cstate.numel(),
+                                  prog.data_ptr<int>(), slot.data_ptr<int>(), ban.data_ptr<int>(), stream());
+}
+
+void constraint_state_init(const Tensor& cstate, int64_t slot, int64_t value) {
+  check_i32(cstate, "constraint state");
+  SHAI_CHECK(cstate.dim() == 1 && slot >= 0 && slot < cstate.numel(), "constraint_state_init: slot ", slot, " of ",
+             cstate.numel(), " state words");
+  SHAI_CHECK(value >= 0 && value < 1024, "constraint_state_init: state ", value, " outside 0..1023");
+  shai::launch_constraint_state_init(cstate.data_ptr<int>(), (int)cstate.numel(), (int)slot, (int)value, stream());
+}
+
 void penalty_state_init(const Tensor& state, int64_t row, const Tensor& tokens, int64_t n_prompt) {
   check_i32(state, "state");
   check_i32(tokens, "tokens");
@@ -2193,6 +2252,10 @@ TORCH_LIBRARY(shai, m) {
   m.def("sample(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out) -> ()");
   m.def("sample_penalized(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out, "
         "Tensor(b!)? state, Tensor state_rows, Tensor rep, Tensor freq, Tensor pres, Tensor min_p) -> ()");
+  m.def("sample_constrained(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out, "
+        "Tensor(b!)? state, Tensor state_rows, Tensor rep, Tensor freq, Tensor pres, Tensor min_p, Tensor pool, "
+        "Tensor(c!) cstate, Tensor prog, Tensor slot, Tensor ban) -> ()");
+  m.def("constraint_state_init(Tensor(a!) cstate, int slot, int value) -> ()");
   m.def("penalty_state_init(Tensor(a!) state, int row, Tensor tokens, int n_prompt) -> ()");
   m.def("token_logprobs(Tensor logits, Tensor tokens, Tensor? row_n, Tensor(a!) vals, Tensor(b!) ids) -> ()");
   m.def("rope_qkv_cache(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor slots, int H, int Hkv, float k_scale=1.0, float v_scale=1.0) -> ()");
@@ -2243,6 +2306,8 @@ TORCH_LIBRARY_IMPL(shai, CUDA, m) {
   m.impl("rope_pairs", &rope_pairs);
   m.impl("sample", &sample);
   m.impl("sample_penalized", &sample_penalized);
+  m.impl("sample_constrained", &sample_constrained);
+  m.impl("constraint_state_init", &constraint_state_init);
   m.impl("penalty_state_init", &penalty_state_init);
   m.impl("token_logprobs", &token_logprobs);
   m.impl("rope_qkv_cache", &rope_qkv_cache);

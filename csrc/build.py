@@ -50,8 +50,8 @@ NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8",
               "kernels/attention_kv8.hip": "flash_fwd_kernelINS_5KvFp8",
               # the fp4 tile GEMM holds up to 128 accumulators beside the widened fragments: every instantiation
               "kernels/gemm_fp4.hip": "gemm_fp4_kernel",
-              # the samplers (plain and penalised) and the log-probability kernel: every instantiation
-              "kernels/sampling.hip": ("sample_kernel", "token_logprobs_kernel"),
+              # the samplers (plain, penalised, constrained) and the log-probability kernel: every instantiation
+              "kernels/sampling.hip": ("sample_kernel", "sample_con_kernel", "token_logprobs_kernel"),
               # the speculative verify attention holds the O^T accumulators of 32 query rows per wave: every form
               "kernels/attention_spec.hip": "spec_attn_kernel"}
 NO_SCRATCH_NAMES = [p for v in NO_SCRATCH.values() for p in ((v,) if isinstance(v, str) else v)]

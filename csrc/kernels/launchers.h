@@ -402,6 +402,18 @@ void launch_sample_penalized(const void* logits, bool bf16, long ld, int B, int 
                              const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
                              int n_state_rows, const int* state_rows, const float* rep, const float* freq,
                              const float* pres, const float* min_p, hipStream_t s);
+// The same with constraint programs (ops/reference.py: con_pack).  pool: the programs' int32 blocks back to back,
+// pool_words long; prog[b]: word offset of row b's program, -1 = the row is unconstrained (exactly the penalised
+// path); cstate [n_slots]: automaton state words, slot[b] row b's; ban[b] != 0 removes the program's stop mask from
+// the allowed tokens this step.  Bias is added before the penalties, disallowed tokens are -inf after them and never
+// returned; the pick advances the row's state word.
+void launch_sample_constrained(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                               const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                               int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                               const float* pres, const float* min_p, const int* pool, long pool_words, int* cstate,
+                               int n_slots, const int* prog, const int* slot, const int* ban, hipStream_t s);
+// cstate[slot] = value (one sequence's automaton state), in stream order.
+void launch_constraint_state_init(int* cstate, int n_slots, int slot, int value, hipStream_t s);
 // Clear one state row (V words) and scatter a token list into it: the first n_prompt tokens set the prompt flag, the
 // rest count as sampled.  Ids outside [0, V) are ignored.
 void launch_penalty_state_init(int* state_row, int V, const int* tokens, int n_tokens, int n_prompt, hipStream_t s);

@@ -21,6 +21,12 @@
 // the candidates with p_i < min_p before the nucleus cut, and the picked token's count is incremented at the end,
 // so the state is current in stream order for the next (look-ahead) step.  Steps 1-3 are shared, as device
 // functions, with token_logprobs_kernel (log-softmax of the raw logits at the picked token and at the top N).
+//
+// The constrained sampler (sample_con_kernel, launch_sample_constrained) is the penalised body once more with the
+// ConLoad policy: + bias before the penalties, -inf after them where the row's automaton state does not allow the
+// token (or the row bans its stop set).  Candidates at -inf are cut with min_p, so a masked token is never returned,
+// and the pick advances the row's state word (one thread, a binary search of the state's edge list) in the same
+// launch.  A row without a program takes exactly the penalised path.
 #include "common.h"
 #include "launchers.h"
 
@@ -58,9 +64,8 @@ struct PenLoad {
   const char* base;
   const int* st;
   float r, f, p;
-  __device__ __forceinline__ float operator()(int i) const {
+  __device__ __forceinline__ float pen(float l, int i) const {
 #pragma clang fp contract(off)
-    float l = smp_load<BF16>(base, i);
     if (st) {
       const int wd = st[i];
       if (wd != 0) {
@@ -72,6 +77,74 @@ struct PenLoad {
       }
     }
     return l;
+  }
+  __device__ __forceinline__ float operator()(int i) const { return pen(smp_load<BF16>(base, i), i); }
+};
+
+// ---- constraint programs (the layout is ops/reference.py's con_pack): CON_HDR header words, then the sections
+constexpr int CON_HDR = 8;
+constexpr int CON_MAX_STATES = 1024;
+constexpr int CON_MAX_BIAS = 300;
+
+// one row's program, resolved from the pool (ok = false: the row is unconstrained)
+struct ConProg {
+  bool ok;
+  int S, W, E, NB;
+  const int *masks, *stop, *plane, *dflt, *estart, *etok, *enext, *bid, *bval;
+};
+
+__device__ __forceinline__ ConProg con_resolve(const int* pool, long pool_words, long off, int V) {
+  ConProg c{};
+  if (!pool || off < 0 || off + CON_HDR > pool_words) return c;
+  const int* h = pool + off;
+  const int S = h[0], W = h[1], E = h[2], NB = h[3], total = h[4];
+  const bool shape = S >= 1 && S <= CON_MAX_STATES && W == (V + 31) / 32 && E >= 0 && NB >= 0 && NB <= CON_MAX_BIAS;
+  const long want = (long)CON_HDR + (long)S * W + 2L * W + S + (S + 1) + 2L * E + 2L * NB;
+  SHAI_DASSERT(shape && total == want && off + want <= pool_words);
+  if (!shape || total != want || off + want > pool_words) return c;
+  c.S = S, c.W = W, c.E = E, c.NB = NB;
+  c.masks = h + CON_HDR;
+  c.stop = c.masks + (long)S * W;
+  c.plane = c.stop + W;
+  c.dflt = c.plane + W;
+  c.estart = c.dflt + S;
+  c.etok = c.estart + S + 1;
+  c.enext = c.etok + E;
+  c.bid = c.enext + E;
+  c.bval = c.bid + NB;
+  c.ok = true;
+  return c;
+}
+
+// the constrained logits of one row: raw, + bias (the list, in LDS, is searched only for tokens the bias plane
+// flags), the penalties, then -inf unless the state's mask (minus the stop mask when the row bans it) has the token's
+// bit.  Lanes of a wave read consecutive tokens, so a wave instruction touches two mask words (one cache line).
+// mask == null: the penalised logits.  Contraction is off as in PenLoad.
+template <bool BF16>
+struct ConLoad {
+  PenLoad<BF16> pl;
+  const int *mask, *stop, *plane;  // stop / plane: null = none
+  const int* bid;                  // LDS
+  const float* bval;               // LDS
+  int nb;
+  __device__ __forceinline__ float operator()(int i) const {
+#pragma clang fp contract(off)
+    float l = smp_load<BF16>(pl.base, i);
+    if (!mask) return pl.pen(l, i);
+    const int wi = i >> 5, bit = i & 31;
+    if (plane && ((plane[wi] >> bit) & 1)) {
+      int lo = 0, hi = nb;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (bid[mid] < i) lo = mid + 1;
+        else hi = mid;
+      }
+      if (lo < nb && bid[lo] == i) l = l + bval[lo];
+    }
+    l = pl.pen(l, i);
+    int m = mask[wi];
+    if (stop) m &= ~stop[wi];
+    return ((m >> bit) & 1) ? l : -INFINITY;
   }
 };
 
@@ -223,12 +296,23 @@ struct PenArgs {
   const float *rep, *freq, *pres, *minp;
 };
 
-template <bool BF16, bool PEN>
-__global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ logits, long ld, int V,
-                                                       const float* __restrict__ temps, const int* __restrict__ topk,
-                                                       const float* __restrict__ topp,
-                                                       const float* __restrict__ uniforms, int* __restrict__ out,
-                                                       PenArgs pa) {
+// per-row constraint inputs of the constrained sampler
+struct ConArgs {
+  const int* pool;   // constraint programs, back to back
+  long pool_words;
+  int* cstate;       // [n_slots] automaton state words
+  int n_slots;
+  const int* prog;   // per row: word offset of its program in the pool, -1 = unconstrained
+  const int* slot;   // per row: its state word
+  const int* ban;    // per row: != 0 bans the program's stop mask this step
+};
+
+// the sampler body; CON implies PEN
+template <bool BF16, bool PEN, bool CON>
+__device__ __forceinline__ void sample_body(const void* __restrict__ logits, long ld, int V,
+                                            const float* __restrict__ temps, const int* __restrict__ topk,
+                                            const float* __restrict__ topp, const float* __restrict__ uniforms,
+                                            int* __restrict__ out, const PenArgs& pa, const ConArgs& ca) {
   __shared__ float cval[SMP_MAXK];
   __shared__ int cidx[SMP_MAXK];
   __shared__ float scan[SMP_MAXK];
@@ -243,13 +327,68 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
   int* st = nullptr;  // this row's state words
   float minp = 0.f;
   int n;
+  [[maybe_unused]] ConProg cp{};          // this row's constraint program, its automaton state and state word
+  [[maybe_unused]] int cst = 0;
+  [[maybe_unused]] int* cslot = nullptr;
+  // the pick's bookkeeping (thread 0): count the token in the penalty state, advance the automaton
+  auto picked = [&](int tok) {
+    if constexpr (PEN) {
+      SHAI_DASSERT(tok >= 0 && tok < V);
+      if (st && tok >= 0 && tok < V) atomicAdd(&st[tok], 1);
+    }
+    if constexpr (CON) {
+      if (cslot) {
+        int lo = cp.estart[cst], hi = cp.estart[cst + 1];
+        SHAI_DASSERT(lo >= 0 && lo <= hi && hi <= cp.E);
+        lo = max(lo, 0), hi = min(hi, cp.E);
+        const int end = hi;
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (cp.etok[mid] < tok) lo = mid + 1;
+          else hi = mid;
+        }
+        int nx = lo < end && cp.etok[lo] == tok ? cp.enext[lo] : cp.dflt[cst];
+        SHAI_DASSERT(nx >= 0 && nx < cp.S);
+        if (nx < 0 || nx >= cp.S) nx = cst;
+        *cslot = nx;
+      }
+    }
+  };
   if constexpr (PEN) {
     const int srow = pa.rows[row];
     SHAI_DASSERT(srow < pa.n_rows);
     if (pa.state && srow >= 0 && srow < pa.n_rows) st = pa.state + (long)srow * V;
     minp = pa.minp[row];
     const PenLoad<BF16> load{base, st, pa.rep[row], pa.freq[row], pa.pres[row]};
-    n = smp_topk<false>(load, V, K, cval, cidx);
+    if constexpr (CON) {
+      __shared__ int s_bid[CON_MAX_BIAS];
+      __shared__ float s_bval[CON_MAX_BIAS];
+      const long off = ca.prog[row];
+      const int sl = ca.slot[row];
+      if (off >= 0) {
+        SHAI_DASSERT(sl >= 0 && sl < ca.n_slots);
+        if (ca.cstate && sl >= 0 && sl < ca.n_slots) {
+          cp = con_resolve(ca.pool, ca.pool_words, off, V);
+          cst = ca.cstate[sl];
+          SHAI_DASSERT(!cp.ok || (cst >= 0 && cst < cp.S));
+          if (cp.ok && (cst < 0 || cst >= cp.S)) cp.ok = false;
+          if (cp.ok) cslot = ca.cstate + sl;
+        }
+      }
+      if (cp.ok) {
+        for (int i = tid; i < cp.NB; i += SMP_T) {
+          s_bid[i] = cp.bid[i];
+          s_bval[i] = __int_as_float(cp.bval[i]);
+        }
+        __syncthreads();
+      }
+      const ConLoad<BF16> cload{load, cp.ok ? cp.masks + (long)cst * cp.W : nullptr,
+                                cp.ok && ca.ban[row] != 0 ? cp.stop : nullptr, cp.ok && cp.NB > 0 ? cp.plane : nullptr,
+                                s_bid, s_bval, cp.NB};
+      n = smp_topk<false>(cload, V, K, cval, cidx);
+    } else {
+      n = smp_topk<false>(load, V, K, cval, cidx);
+    }
   } else {
     const RawLoad<BF16> load{base};
     n = smp_topk<BF16>(load, V, K, cval, cidx);
@@ -258,10 +397,7 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
     if (tid == 0) {
       const int tok = cidx[0];
       out[row] = tok;
-      if constexpr (PEN) {
-        SHAI_DASSERT(tok >= 0 && tok < V);
-        if (st && tok >= 0 && tok < V) atomicAdd(&st[tok], 1);
-      }
+      picked(tok);
     }
     return;
   }
@@ -274,7 +410,10 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
     __shared__ int s_n2;
     if (tid == 0) s_n2 = 0;
     __syncthreads();
-    const bool stay = tid < n && (tid == 0 || !(p < minp));
+    // (constrained: candidates at -inf go too -- masked tokens, a suffix as well; candidate 0 is finite)
+    bool fin = true;
+    if constexpr (CON) fin = tid < n && cval[tid] > -INFINITY;
+    const bool stay = tid < n && (tid == 0 || (!(p < minp) && fin));
     if (stay) atomicAdd(&s_n2, 1);
     else p = 0.f;
     __syncthreads();
@@ -322,11 +461,27 @@ __global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ 
   if (tid == 0) {
     const int tok = cidx[min(s_pick, L - 1)];
     out[row] = tok;
-    if constexpr (PEN) {
-      SHAI_DASSERT(tok >= 0 && tok < V);
-      if (st && tok >= 0 && tok < V) atomicAdd(&st[tok], 1);
-    }
+    picked(tok);
   }
+}
+
+template <bool BF16, bool PEN>
+__global__ void __launch_bounds__(SMP_T) sample_kernel(const void* __restrict__ logits, long ld, int V,
+                                                       const float* __restrict__ temps, const int* __restrict__ topk,
+                                                       const float* __restrict__ topp,
+                                                       const float* __restrict__ uniforms, int* __restrict__ out,
+                                                       PenArgs pa) {
+  sample_body<BF16, PEN, false>(logits, ld, V, temps, topk, topp, uniforms, out, pa, ConArgs{});
+}
+
+template <bool BF16>
+__global__ void __launch_bounds__(SMP_T) sample_con_kernel(const void* __restrict__ logits, long ld, int V,
+                                                           const float* __restrict__ temps,
+                                                           const int* __restrict__ topk,
+                                                           const float* __restrict__ topp,
+                                                           const float* __restrict__ uniforms, int* __restrict__ out,
+                                                           PenArgs pa, ConArgs ca) {
+  sample_body<BF16, true, true>(logits, ld, V, temps, topk, topp, uniforms, out, pa, ca);
 }
 
 void launch_sample(const void* logits, bool bf16, long ld, int B, int V, const float* temps, const int* top_k,
@@ -343,6 +498,28 @@ void launch_sample_penalized(const void* logits, bool bf16, long ld, int B, int 
   const PenArgs pa{state, n_state_rows, state_rows, rep, freq, pres, min_p};
   if (bf16) sample_kernel<true, true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa);
   else sample_kernel<false, true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa);
+}
+
+void launch_sample_constrained(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                               const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                               int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                               const float* pres, const float* min_p, const int* pool, long pool_words, int* cstate,
+                               int n_slots, const int* prog, const int* slot, const int* ban, hipStream_t s) {
+  const PenArgs pa{state, n_state_rows, state_rows, rep, freq, pres, min_p};
+  const ConArgs ca{pool, pool_words, cstate, n_slots, prog, slot, ban};
+  if (bf16) sample_con_kernel<true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa, ca);
+  else sample_con_kernel<false><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa, ca);
+}
+
+// ---- constraint state: (re)initialise one sequence's automaton state word (stream-ordered: it lands after every
+// launch enqueued before it, a look-ahead step of the slot's previous owner included)
+__global__ void constraint_state_init_kernel(int* __restrict__ cstate, int n_slots, int slot, int value) {
+  SHAI_DASSERT(slot >= 0 && slot < n_slots);
+  if (threadIdx.x == 0 && blockIdx.x == 0 && slot >= 0 && slot < n_slots) cstate[slot] = value;
+}
+
+void launch_constraint_state_init(int* cstate, int n_slots, int slot, int value, hipStream_t s) {
+  constraint_state_init_kernel<<<1, 64, 0, s>>>(cstate, n_slots, slot, value);
 }
 
 // ---- penalty state: (re)initialise one row.  Workgroup b owns PSI_SPAN consecutive words: it clears them, then

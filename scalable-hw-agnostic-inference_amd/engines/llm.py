@@ -54,6 +54,7 @@ from .. import ops
 from . import capture, new_graph
 from ..models.llama import (KV_BLOCK, Batch, LlamaConfig, LlamaForCausalLM, allocate_kv_cache, kv_bytes_per_block)
 from ..parallel.state import tp
+from . import constraints
 from ..weights import materialize
 
 
@@ -72,6 +73,17 @@ class SamplingParams:
     frequency_penalty: float = 0.0       # [-2, 2]; subtracted per sampled occurrence
     min_p: float = 0.0                   # [0, 1]; candidates below min_p x the top probability are dropped (before top-p)
     logprobs: Optional[int] = None       # None, or 0..20 top log-probabilities per generated token
+    # constraints (engines/constraints.py compiles them to one program the sampler kernel runs), neutral by default
+    logit_bias: Optional[Dict[int, float]] = None        # <= 300 entries, values in [-100, 100]; added before the penalties
+    allowed_token_ids: Optional[List[int]] = None        # only these may be sampled (EOS / stop tokens only if listed)
+    bad_words_ids: Optional[List[List[int]]] = None      # token sequences the output must not contain
+    min_tokens: int = 0                                  # EOS and stop_token_ids are masked before this many tokens
+    guided_choice: Optional[List[List[int]]] = None      # the output is one of these token sequences, then a stop token
+
+    @property
+    def constrained(self) -> bool:
+        """Whether the sequence needs a constraint program."""
+        return constraints.needed(self)
 
     @property
     def penalised(self) -> bool:
@@ -91,6 +103,7 @@ class SamplingParams:
         n = self.logprobs
         if n is not None and not (isinstance(n, numbers.Integral) and not isinstance(n, bool) and 0 <= n <= ops.LOGPROBS_MAX):
             raise ValueError(f"logprobs must be None or an integer in 0..{ops.LOGPROBS_MAX}, got {n!r}")
+        constraints.validate(self)
 
 
 @dataclass(eq=False)  # identity semantics: membership tests must not deep-compare prompts (O(B^2))
@@ -114,6 +127,8 @@ class Sequence_:
     n_prompt0: int = 0                                           # original prompt length (preemption grows ``prompt``)
     pen_row: int = -1                                            # row of the engine's penalty-state table, -1: none
     logprobs: List[dict] = field(default_factory=list)           # one entry per output token (params.logprobs set)
+    con: Optional[object] = None                                 # the constraint pool's entry of its program (held)
+    con_slot: int = -1                                           # its automaton state word, -1: none
 
     @property
     def tokens(self) -> List[int]:
@@ -410,14 +425,17 @@ class _DecodeGraph:
     NF = 9  # per-row int32 fields before the block table (6 more in a penalised / logprobs program)
 
     def __init__(self, engine: "LLMEngine", Bc: int, cross: bool = False, greedy: bool = False,
-                 splits: Optional[int] = None, full_vocab: bool = False, pen: int = 0, lp: bool = False):
+                 splits: Optional[int] = None, full_vocab: bool = False, pen: int = 0, lp: bool = False,
+                 con: bool = False):
         self.Bc = Bc
         # pen: 0 today's sampler; 1 the penalised sampler without a state table (min_p only); 2 with the table (its
         # address is captured).  lp: the log-probability kernel runs after the sampler.  Either adds the per-row
         # fields state row / repetition / frequency / presence / min_p / logprobs count to the step's buffer.
-        self.pen, self.lp = pen, lp
-        if pen or lp:
-            self.NF = 15
+        # con: the constrained sampler (the constraint pool's and the state words' addresses are captured); adds the
+        # per-row fields program offset / state slot / ban_stop behind those six.
+        self.pen, self.lp, self.con = pen, lp, con
+        if pen or lp or con:
+            self.NF = 18 if con else 15
         # full_vocab: some row samples with top_k <= 0 (or > 1024) -- the fused sampler keeps 1024 candidates,
         # so such steps publish the logits from the graph and sample them exactly over the whole vocabulary
         # (torch top-k / top-p path, same inverse-CDF rule at the same uniforms) after the replay
@@ -431,12 +449,15 @@ class _DecodeGraph:
         self.ids, self.pos, self.slots, self.lens, self.topk = f(0), f(1), f(2), f(3), f(4)
         self.temps, self.topp, self.u = f(5).view(torch.float32), f(6).view(torch.float32), f(7).view(torch.float32)
         self.rowmap = f(8)
-        if pen or lp:
+        if pen or lp or con:
             self.prow, self.nlp = f(9), f(14)
             self.rep, self.freq, self.pres, self.minp = (f(i).view(torch.float32) for i in (10, 11, 12, 13))
             self.prow.fill_(-1)
             self.nlp.fill_(-1)
             self.rep.fill_(1.0)
+        if con:
+            self.cprog, self.cslot, self.cban = f(15), f(16), f(17)
+            self.cprog.fill_(-1)
         if lp:   # [2, Bc, 1 + N]: log-probabilities (fp32 bits) and token ids, one device->host copy per step
             self.lp_buf = torch.zeros(2, Bc, 1 + ops.LOGPROBS_MAX, dtype=torch.int32, device=dev)
         self.bt = self.dbuf[self.NF * Bc:].view(Bc, mb)
@@ -485,7 +506,7 @@ class _DecodeGraph:
             return
         if self.greedy:
             self.toks.copy_(logits.float().argmax(-1))
-        elif self.pen:
+        elif self.pen or self.con:
             self._sample_pen(logits)
         elif logits.is_cuda:   # full_vocab=False: no host-side inspection of the (captured) top-k values
             sample(logits, self.temps, self.topk, self.topp, uniforms=self.u, out=self.toks, full_vocab=False)
@@ -496,8 +517,15 @@ class _DecodeGraph:
             self._logprobs(logits)
 
     def _sample_pen(self, logits, full_vocab=False):
+        eng = self.engine
+        if self.con:
+            ops.sample_constrained(logits, self.temps, self.topk, self.topp, self.u, self.toks,
+                                   eng.pen_state if self.pen == 2 else None, self.prow, self.rep, self.freq,
+                                   self.pres, self.minp, eng.con_pool.buf, eng.con_state, self.cprog, self.cslot,
+                                   self.cban, full_vocab=full_vocab)
+            return
         ops.sample_penalized(logits, self.temps, self.topk, self.topp, self.u, self.toks,
-                             self.engine.pen_state if self.pen == 2 else None, self.prow, self.rep, self.freq,
+                             eng.pen_state if self.pen == 2 else None, self.prow, self.rep, self.freq,
                              self.pres, self.minp, full_vocab=full_vocab)
 
     def _logprobs(self, logits):
@@ -522,7 +550,16 @@ class _DecodeGraph:
         v(6).view(np.float32)[:B] = [s.params.top_p for s in seqs]
         v(7).view(np.float32)[:B] = uniforms
         v(8)[:B] = rowmap
-        if self.pen or self.lp:
+        if self.con:   # (ban_stop: lens - 1 is the context before the sampled token, whichever step enqueues it)
+            v(15)[:B] = [-1 if s.con is None else s.con.off for s in seqs]
+            v(16)[:B] = [s.con_slot for s in seqs]
+            v(17)[:B] = [int(s.con is not None and
+                             ops.ref.ban_stop(int(n) - s.n_prompt0, s.params.min_tokens)) for s, n in zip(seqs, lens)]
+            if B < Bc:
+                v(15)[B:] = -1
+                v(16)[B:] = -1
+                v(17)[B:] = 0
+        if self.pen or self.lp or self.con:
             v(9)[:B] = [s.pen_row for s in seqs]
             v(10).view(np.float32)[:B] = [s.params.repetition_penalty for s in seqs]
             v(11).view(np.float32)[:B] = [s.params.frequency_penalty for s in seqs]
@@ -572,8 +609,8 @@ class _DecodeGraph:
             self._program()
         eng = self.engine
         if self.full_vocab:   # exact full-vocabulary top-k / top-p at the same uniforms, outside the graph
-            if self.pen:      # ... with penalties and min_p: the oracle's rule on the device, state counted too
-                self._sample_pen(self.logits, full_vocab=True)
+            if self.pen or self.con:   # ... with penalties, min_p, constraints: the oracle's rule on the device, the
+                self._sample_pen(self.logits, full_vocab=True)   # states counted / advanced too
             else:
                 self.toks.copy_(sample(self.logits, self.temps, self.topk, self.topp, uniforms=self.u,
                                        full_vocab=True))
@@ -751,6 +788,11 @@ class LLMEngine:
         self.pen_state: Optional[torch.Tensor] = None
         self._pen_free: List[int] = list(range(max_num_seqs - 1, -1, -1))
         self._lp_host: Optional[List[torch.Tensor]] = None
+        # constraints: the pool of program blocks and one automaton state word per sequence slot, both allocated by
+        # the first constrained request and never moved (decode graphs capture their addresses)
+        self.con_pool: Optional[constraints.ConstraintPool] = None
+        self.con_state: Optional[torch.Tensor] = None
+        self._con_free: List[int] = list(range(max_num_seqs - 1, -1, -1))
         self.stats = {"prefill_tokens": 0, "decode_tokens": 0, "steps": 0, "prefix_hit_tokens": 0}
         if self.speculative is not None:   # verify steps run, draft tokens proposed, draft tokens accepted
             self.stats.update(spec_steps=0, spec_drafted=0, spec_accepted=0)
@@ -839,9 +881,10 @@ class LLMEngine:
                 at = 1 if prompt and prompt[0] == self.cfg.bos_token_id else 0
                 prompt = prompt[:at] + [itok] + prompt[at:]
             pos = prompt.index(itok)
+        con = self._con_acquire(params) if params.constrained else None   # (last: nothing after it can fail)
         sid = next(self._ids)
         key = (int(params.seed) & ((1 << 63) - 1)) | (1 << 63) if params.seed is not None else (self.seed << 32) + sid
-        s = Sequence_(sid, prompt, params, image=img, img_pos=pos, rng_key=key, n_prompt0=len(prompt))
+        s = Sequence_(sid, prompt, params, image=img, img_pos=pos, rng_key=key, n_prompt0=len(prompt), con=con)
         self.waiting.append(s)
         return s
 
@@ -854,6 +897,44 @@ class LLMEngine:
             raise MemoryError(f"no room for the penalty-state table ({n} x {V} int32 = {4 * n * V / 2**20:.0f} MiB); "
                               "lower gpu_memory_utilization or max_num_seqs, or send the request without "
                               f"repetition / presence / frequency penalties: {e}") from None
+
+    def _stop_ids(self, params: SamplingParams) -> set:
+        """The token ids that end a request of these options."""
+        return set(params.stop_token_ids or []) | (set() if params.ignore_eos else self.eos)
+
+    def _con_acquire(self, params: SamplingParams):
+        """Compile (or find) the request's constraint program and reserve it in the pool: ValueError for options that
+        do not compile, MemoryError when the pool cannot be allocated or the program does not fit it -- either fails
+        this request alone."""
+        V, stop = self.cfg.vocab_size, self._stop_ids(params)
+        key = constraints.program_key(params, stop, V)
+        make = lambda: constraints.compile_program(params, stop, V)
+        if self.con_pool is None:
+            prog = make()       # (options that do not compile allocate nothing)
+            make = lambda: prog
+            with torch.inference_mode(False):   # written from inside and outside inference mode
+                pool = constraints.ConstraintPool(self.device)
+                try:
+                    state = torch.zeros(self.max_num_seqs, dtype=torch.int32, device=self.device)
+                except (RuntimeError, MemoryError) as e:
+                    raise MemoryError(f"no room for the constraint state words: {e}") from None
+                entry = pool.acquire(key, make)     # (a program larger than the pool: nothing is kept)
+            self.con_pool, self.con_state = pool, state
+            return entry
+        with torch.inference_mode(False):
+            return self.con_pool.acquire(key, make)
+
+    def _con_drop(self, entry) -> None:
+        if entry is not None:
+            self.con_pool.release(entry)
+
+    def _con_attach(self, s: Sequence_) -> None:
+        """Give an admitted constrained sequence its state word, initialised by replaying what it has generated so far
+        (a preempted sequence carries it in ``prompt``) through the host automaton."""
+        if s.con is None or s.con_slot >= 0:
+            return
+        s.con_slot = self._con_free.pop()
+        ops.constraint_state_init(self.con_state, s.con_slot, s.con.prog.replay(s.tokens[s.n_prompt0:]))
 
     def lp_host_buf(self, i: int) -> torch.Tensor:
         """Pinned host buffer ``i`` (of two) for a step's logprobs, allocated with the first request that asks."""
@@ -888,6 +969,9 @@ class LLMEngine:
             if s.blocks or s.cross_blocks:
                 self._free(s)
             s.finished, s.finish_reason = True, "abort"
+            if s.con is not None:
+                self._con_drop(s.con)
+                s.con = None
         self.waiting, self.running = [], []
         return gone
 
@@ -908,6 +992,12 @@ class LLMEngine:
         if s.pen_row >= 0:   # (a look-ahead step still in flight may count one more token in the row: the next
             self._pen_free.append(s.pen_row)   # owner's init launch clears it, later in stream order)
             s.pen_row = -1
+        if s.con_slot >= 0:  # (the same holds for the automaton state word)
+            self._con_free.append(s.con_slot)
+            s.con_slot = -1
+        if s.finished and s.con is not None:   # (a preempted sequence keeps its program)
+            self._con_drop(s.con)
+            s.con = None
 
     def _prefix_hashes(self, toks: Sequence[int], n_full: int) -> List[int]:
         hs, h = [], 0
@@ -956,6 +1046,7 @@ class LLMEngine:
             s.prefill_started = True
             s._hashes = []
             self._pen_attach(s)
+            self._con_attach(s)
             if self.prefix_caching and s.image is None:  # image prompts: K/V depend on the image, not cached
                 n_full = (len(s.prompt) - 1) // KV_BLOCK
                 hs = self._prefix_hashes(s.prompt, n_full)
@@ -1084,12 +1175,12 @@ class LLMEngine:
 
     def _spec_ok(self, seqs) -> bool:
         """Whether a pure decode step of ``seqs`` may run as a verify step: speculation is on and no sequence needs a
-        penalty-state row, min_p, logprobs or the full-vocabulary sampler (those steps take the plain path)."""
+        penalty-state row, min_p, logprobs, constraints or the full-vocabulary sampler (those steps take the plain path)."""
         if self.proposer is None:
             return False
         for s in seqs:
             p = s.params
-            if s.pen_row >= 0 or p.penalised or p.min_p > 0 or p.logprobs is not None:
+            if s.pen_row >= 0 or p.penalised or p.min_p > 0 or p.logprobs is not None or s.con is not None:
                 return False
             if p.temperature > 0 and not 0 < p.top_k <= ops.SAMPLER_MAX_K:
                 return False
@@ -1160,17 +1251,20 @@ class LLMEngine:
         cross = self._cross_tables(seqs) if any(s.cross_blocks for s in seqs) else None
         all_greedy = all(s.params.temperature <= 0 for s in seqs)
         pen, lp = self._pen_kind(seqs), any(s.params.logprobs is not None for s in seqs)
-        greedy = all_greedy and not pen   # greedy rows of a penalised batch need penalised logits: the sampler
+        con = any(s.con is not None for s in seqs)
+        greedy = all_greedy and not pen and not con   # greedy rows of such a batch need the sampler's logits
         splits = self.decode_splits(Bc, int(lens.max()) if B else 0)
         full = (not all_greedy) and any(s.params.temperature > 0 and not 0 < s.params.top_k <= ops.SAMPLER_MAX_K
                                         for s in seqs)
         key = (Bc, cross is not None, greedy, splits) + ((True,) if full else ())
         if pen or lp:   # (steps with neither keep the keys and programs they always had)
             key += (("pen", pen, "logprobs", lp),)
+        if con:
+            key += (("con",),)
         g = self._graphs.get(key)
         if g is None:
             g = self._graphs[key] = _DecodeGraph(self, Bc, cross=cross is not None, greedy=greedy, splits=splits,
-                                                 full_vocab=full, pen=pen, lp=lp)
+                                                 full_vocab=full, pen=pen, lp=lp, con=con)
         # noise for the token each row samples, at absolute position ctx_before + 1
         u = (seq_uniforms([s.rng_key for s in seqs], [c + 1 for c in ctx_before]) if not all_greedy
              else np.zeros(B, np.float32))
@@ -1250,21 +1344,28 @@ class LLMEngine:
         u = None if greedy else torch.from_numpy(seq_uniforms([s.rng_key for s in seqs],
                                                               [s.length for s in seqs])).to(d)
         pen, lp = self._pen_kind(seqs), any(s.params.logprobs is not None for s in seqs)
-        if not pen and not lp:
+        con = any(s.con is not None for s in seqs)
+        if not pen and not lp and not con:
             self._append(seqs, sample(logits, temps, tk, tpp, self.gen, all_greedy=greedy, uniforms=u).tolist())
             return
         # the same ops as the decode program: penalised sampler (counts the picked tokens), then logprobs
         f32 = lambda xs: torch.tensor(xs, dtype=torch.float32, device=d)
         toks = torch.empty(len(seqs), dtype=torch.int32, device=d)
-        if pen:
+        if pen or con:
             full = any(s.params.temperature > 0 and not 0 < s.params.top_k <= ops.SAMPLER_MAX_K for s in seqs)
-            ops.sample_penalized(logits, temps, tk.int(), tpp, u if u is not None else torch.zeros_like(temps), toks,
-                                 self.pen_state if pen == 2 else None,
-                                 torch.tensor([s.pen_row for s in seqs], dtype=torch.int32, device=d),
-                                 f32([s.params.repetition_penalty for s in seqs]),
-                                 f32([s.params.frequency_penalty for s in seqs]),
-                                 f32([s.params.presence_penalty for s in seqs]),
-                                 f32([s.params.min_p for s in seqs]), full_vocab=full)
+            i32 = lambda xs: torch.tensor(xs, dtype=torch.int32, device=d)
+            args = (logits, temps, tk.int(), tpp, u if u is not None else torch.zeros_like(temps), toks,
+                    self.pen_state if pen == 2 else None, i32([s.pen_row for s in seqs]),
+                    f32([s.params.repetition_penalty for s in seqs]), f32([s.params.frequency_penalty for s in seqs]),
+                    f32([s.params.presence_penalty for s in seqs]), f32([s.params.min_p for s in seqs]))
+            if con:
+                ban = [int(s.con is not None and ops.ref.ban_stop(s.length - s.n_prompt0, s.params.min_tokens))
+                       for s in seqs]
+                ops.sample_constrained(*args, self.con_pool.buf, self.con_state,
+                                       i32([-1 if s.con is None else s.con.off for s in seqs]),
+                                       i32([s.con_slot for s in seqs]), i32(ban), full_vocab=full)
+            else:
+                ops.sample_penalized(*args, full_vocab=full)
         else:
             toks.copy_(sample(logits, temps, tk, tpp, self.gen, all_greedy=greedy, uniforms=u))
         lps = None
@@ -1286,8 +1387,7 @@ class LLMEngine:
                 s.logprobs.append(lps[i])
             if s.first_token_time is None:
                 s.first_token_time = now
-            stop = set(s.params.stop_token_ids or []) | (set() if s.params.ignore_eos else self.eos)
-            if tok in stop:
+            if tok in self._stop_ids(s.params):
                 s.finished, s.finish_reason = True, "stop"
             elif len(s.output) >= s.params.max_tokens or s.length >= self.max_model_len:
                 s.finished, s.finish_reason = True, "length"

@@ -30,6 +30,7 @@ __all__ = [
     "paged_attention_varlen", "rope_qkv_cache", "quantize_kv_fp8", "dequant_kv_fp8", "kv_dequant_blocks",
     "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE", "resolve_kv_prefill", "KV_PREFILL_ROUTES",
     "sample_penalized", "penalty_state_init", "token_logprobs", "LOGPROBS_MAX",
+    "sample_constrained", "constraint_state_init",
 ]
 
 
@@ -1037,6 +1038,33 @@ def sample_penalized(logits, temps, top_k, top_p, uniforms, out, state, state_ro
     _K().sample_penalized(logits.contiguous(), temps, top_k, top_p, uniforms, out, state, state_rows, rep, freq,
                           pres, min_p)
     return out
+
+
+def sample_constrained(logits, temps, top_k, top_p, uniforms, out, state, state_rows, rep, freq, pres, min_p, pool,
+                       cstate, prog, slot, ban, full_vocab=False):
+    """``sample_penalized`` under constraint programs (``reference.con_pack``), into ``out`` (int32).  ``pool``: int32
+    [P], the programs back to back; ``prog[b]``: word offset of row b's program, -1 = unconstrained (exactly the
+    penalised path); ``cstate``: int32 [slots] automaton state words, ``slot[b]`` row b's; ``ban[b]`` != 0 removes the
+    program's stop mask this step.  The same call counts the picked tokens in ``state`` and advances the state words.
+    On the GPU one fused kernel; ``full_vocab`` and CPU tensors run the oracle (``reference.sample_constrained``)."""
+    if not _gpu(logits) or full_vocab:
+        out.copy_(ref.sample_constrained(logits, temps, top_k, top_p, uniforms, state, state_rows, rep, freq, pres,
+                                         min_p, pool, cstate, prog, slot, ban))
+        return out
+    _K().sample_constrained(logits.contiguous(), temps, top_k, top_p, uniforms, out, state, state_rows, rep, freq,
+                            pres, min_p, pool, cstate, prog, slot, ban)
+    return out
+
+
+def constraint_state_init(cstate, slot, value):
+    """``cstate[slot] = value`` (one sequence's automaton state) as one stream-ordered launch."""
+    if not 0 <= int(slot) < cstate.numel() or not 0 <= int(value) < ref.CON_MAX_STATES:
+        raise ValueError(f"constraint_state_init: slot {slot} of {cstate.numel()}, state {value}")
+    if not _gpu(cstate):
+        cstate[int(slot)] = int(value)
+        return cstate
+    _K().constraint_state_init(cstate, int(slot), int(value))
+    return cstate
 
 
 def penalty_state_init(state, row, tokens, n_prompt):

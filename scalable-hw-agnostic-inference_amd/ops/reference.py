@@ -656,7 +656,8 @@ def sample_candidates(l, temps, top_k, top_p, min_p, uniforms, dtype=torch.float
     """The sampling rule on (already penalised) fp32 logits ``l`` [B, V]: greedy rows (temperature <= 0) take the
     first index of the maximum; the others sort the top-k candidates (descending value, ascending index), weigh them
     p_i = exp((l_i - l_0) / T), drop p_i < min_p (candidate 0 stays), keep candidate i of the survivors while the
-    mass before it is <= top_p of their total, and draw by inverse CDF at the uniform.  ``dtype``: precision of the
+    mass before it is <= top_p of their total, and draw by inverse CDF at the uniform.  Candidates whose value is
+    -inf are dropped with the min_p cut (candidate 0 must be finite).  ``dtype``: precision of the
     probabilities.  ``return_kept``: also the [B, V] mask of the tokens that can be drawn."""
     B, V = l.shape
     vals, idx = torch.sort(l, dim=-1, descending=True, stable=True)
@@ -665,7 +666,9 @@ def sample_candidates(l, temps, top_k, top_p, min_p, uniforms, dtype=torch.float
     greedy = temps <= 0
     T = torch.where(greedy, torch.ones_like(temps), temps).to(dtype)[:, None]
     p = torch.exp((vals - vals[:, :1]).to(dtype) / T)
-    keep = (ar < k) & ((p >= min_p.to(dtype)[:, None]) | (ar == 0))
+    # (candidates at -inf -- tokens a constraint masks -- go before the min_p cut: they are a suffix of the sorted
+    # candidates, and a masked token is never returned whatever top_k, top_p and the uniform are)
+    keep = (ar < k) & (((p >= min_p.to(dtype)[:, None]) & (vals > float("-inf"))) | (ar == 0))
     p = p * keep
     cum = p.cumsum(-1)
     keep = keep & ((cum - p) <= top_p.to(dtype)[:, None] * cum[:, -1:])
@@ -716,3 +719,182 @@ def token_logprobs(logits, tokens, n, row_n=None, dtype=torch.float32):
         gone = (torch.arange(1 + n, device=logits.device)[None, :] > cnt)
         ids, vals = ids.masked_fill(gone, -1), vals.masked_fill(gone, float("-inf"))
     return vals.to(torch.float32 if dtype == torch.float32 else dtype), ids.to(torch.int32)
+
+
+# ---------------------------------------------------------------------- constrained sampling
+# The oracle of the constrained sampler (csrc/kernels/sampling.hip, sample_con_kernel).  A constraint PROGRAM is an
+# immutable block of int32 words (``con_pack``); programs lie back to back in a pool and a row names its program by
+# the block's word offset (-1: the row is unconstrained).  Block layout, CON_HDR header words then the sections:
+#   header   S (states), W = ceil(V / 32), E (edges), NB (bias entries), total words of the block, 0, 0, 0
+#   masks    [S, W]  allow-mask of every state: bit i & 31 of word i >> 5 set = token i allowed; pad bits zero
+#   stop     [W]     the EOS ids and the request's stop_token_ids (removed from the mask of a row with ban_stop set)
+#   plane    [W]     "has a bias" bits: the bias list is searched for flagged tokens only
+#   default  [S]     next state of a token without an edge
+#   estart   [S + 1] edges of state s: etok / enext [estart[s], estart[s + 1]), tokens ascending
+#   etok, enext [E]
+#   bid, bval   [NB] bias ids (ascending) and fp32 values (bit patterns)
+# The mutable part is one int32 state word per sequence slot (``cstate``), advanced by the sampler after its pick.
+CON_HDR = 8
+CON_MAX_STATES = 1024
+CON_MAX_BIAS = 300
+
+
+def con_words(V):
+    return (int(V) + 31) // 32
+
+
+def con_mask(ids, V):
+    """int32 [W] allow-mask with the bits of ``ids`` set (ids outside [0, V) are ignored; pad bits stay zero)."""
+    bits = torch.zeros(con_words(V) * 32, dtype=torch.bool)
+    ids = torch.as_tensor(list(ids), dtype=torch.int64).reshape(-1)
+    bits[ids[(ids >= 0) & (ids < V)]] = True
+    return con_mask_pack(bits)
+
+
+def con_mask_pack(bits):
+    """bool [..., 32 * W] -> int32 [..., W]."""
+    w = (bits.reshape(*bits.shape[:-1], -1, 32).long() << torch.arange(32)).sum(-1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def con_mask_bits(words, V):
+    """int32 [..., W] -> bool [..., V]."""
+    sh = torch.arange(32, device=words.device)
+    return (((words.long()[..., None] >> sh) & 1) != 0).reshape(*words.shape[:-1], -1)[..., :V]
+
+
+def con_pack(V, masks, stop, default, edges, bias=()):
+    """The int32 block of one program.  masks: int32 [S, W]; stop: int32 [W]; default: S next states; edges: per
+    state a list of (token, next state), tokens ascending; bias: (id, value) pairs, ids ascending."""
+    import numpy as np
+    S, W = masks.shape
+    assert W == con_words(V) and len(default) == S and len(edges) == S and stop.numel() == W
+    estart, etok, enext = [0], [], []
+    for es in edges:
+        etok += [int(t) for t, _ in es]
+        enext += [int(n) for _, n in es]
+        estart.append(len(etok))
+    bid = [int(i) for i, _ in bias]
+    bval = np.asarray([v for _, v in bias], dtype=np.float32).view(np.int32).tolist()
+    total = CON_HDR + S * W + 2 * W + S + (S + 1) + 2 * len(etok) + 2 * len(bid)
+    i32 = lambda xs: torch.tensor(xs, dtype=torch.int32)
+    blk = torch.cat([i32([S, W, len(etok), len(bid), total, 0, 0, 0]), masks.reshape(-1).to(torch.int32),
+                     stop.to(torch.int32), con_mask(bid, V), i32(list(default)), i32(estart), i32(etok), i32(enext),
+                     i32(bid), i32(bval)])
+    assert blk.numel() == total
+    return blk
+
+
+def con_view(pool, off, V):
+    """The sections of the program at word offset ``off`` of ``pool`` (views), or None if there is no valid block."""
+    from types import SimpleNamespace
+    n = pool.numel()
+    if off < 0 or off + CON_HDR > n:
+        return None
+    S, W, E, NB, total = pool[off:off + 5].tolist()
+    if not (1 <= S <= CON_MAX_STATES and W == con_words(V) and E >= 0 and 0 <= NB <= CON_MAX_BIAS):
+        return None
+    if total != CON_HDR + S * W + 2 * W + S + (S + 1) + 2 * E + 2 * NB or off + total > n:
+        return None
+    o, out = off + CON_HDR, SimpleNamespace(S=S, W=W, E=E, NB=NB, total=total)
+    for name, k in (("masks", S * W), ("stop", W), ("plane", W), ("default", S), ("estart", S + 1), ("etok", E),
+                    ("enext", E), ("bid", NB), ("bval", NB)):
+        setattr(out, name, pool[o:o + k])
+        o += k
+    out.masks = out.masks.view(S, W)
+    out.bval = out.bval.view(torch.float32)
+    return out
+
+
+def con_rows(pool, cstate, prog, slot, V):
+    """Per batch row (program view, state word index, state) or None where the row is unconstrained (no program, or
+    a slot / state out of range: the kernel takes the penalised path for such a row too)."""
+    out = []
+    if pool is None or cstate is None:
+        return [None] * prog.numel()
+    views = {}
+    states = cstate.tolist()
+    for off, sl in zip(prog.tolist(), slot.tolist()):
+        if off < 0 or not 0 <= sl < len(states):
+            out.append(None)
+            continue
+        if off not in views:
+            views[off] = con_view(pool, off, V)
+        pv = views[off]
+        out.append((pv, sl, states[sl]) if pv is not None and 0 <= states[sl] < pv.S else None)
+    return out
+
+
+def con_next(pv, state, tok):
+    """The automaton's step: the edge of ``tok`` out of ``state``, else the state's default."""
+    lo, hi = int(pv.estart[state]), int(pv.estart[state + 1])
+    toks = pv.etok[lo:hi].tolist()
+    import bisect
+    j = bisect.bisect_left(toks, tok)
+    if j < len(toks) and toks[j] == tok:
+        return int(pv.enext[lo + j])
+    return int(pv.default[state])
+
+
+def ban_stop(generated, min_tokens):
+    """The per-step flag of a row: EOS and the stop tokens are masked while fewer than ``min_tokens`` tokens have been
+    generated."""
+    return generated < min_tokens
+
+
+def constrain_logits(logits, words, rep, freq, pres, rows, ban, pad_allowed=False, bias_last=False):
+    """The constrained fp32 logits: raw, + bias where the token has one, the penalties (``penalize_logits``), then
+    -inf where the current state does not allow the token or ``ban`` is set and the token is in the stop mask.
+    ``rows``: ``con_rows``.  (pad_allowed / bias_last: mutants of the rule, for the tests.)"""
+    B, V = logits.shape
+    l = logits.float()
+    bias = torch.zeros_like(l)
+    has = torch.zeros(B, V, dtype=torch.bool, device=l.device)
+    allowed = torch.ones(B, V, dtype=torch.bool, device=l.device)
+    for b, r in enumerate(rows):
+        if r is None:
+            continue
+        pv, _, st = r
+        if pv.NB:
+            ids = pv.bid.long()
+            has[b, ids] = True
+            bias[b, ids] = pv.bval
+        m = pv.masks[st]
+        if int(ban[b]) != 0:
+            m = m & ~pv.stop
+        allowed[b] = con_mask_bits(m, V)
+        if pad_allowed and V % 32:
+            allowed[b, V - V % 32:] = True
+    if not bias_last:
+        l = torch.where(has, l + bias, l)
+    l = penalize_logits(l, words, rep, freq, pres)
+    if bias_last:
+        l = torch.where(has, l + bias, l)
+    return torch.where(allowed, l, torch.full_like(l, float("-inf")))
+
+
+def con_advance(cstate, rows, toks):
+    """What the sampler does after picking: state' = edge(state, token), else the state's default."""
+    for r, t in zip(rows, toks.tolist()):
+        if r is not None:
+            cstate[r[1]] = con_next(r[0], r[2], int(t))
+
+
+def sample_constrained(logits, temps, top_k, top_p, uniforms, state, rows, rep, freq, pres, min_p, pool, cstate, prog,
+                       slot, ban, dtype=torch.float32, update=True):
+    """Constrain, penalise, sample; count the picked tokens in ``state`` and advance the automaton states in
+    ``cstate`` (what the fused kernel does in one launch)."""
+    B, V = logits.shape
+    words = None
+    if state is not None and rows is not None:
+        words = penalty_words(state, rows, B, V, logits.device)
+    crows = con_rows(pool, cstate, prog, slot, V)
+    l = constrain_logits(logits, words, rep, freq, pres, crows, ban)
+    if min_p is None:
+        min_p = torch.zeros(B, dtype=torch.float32, device=logits.device)
+    toks = sample_candidates(l, temps.float(), top_k.long(), top_p.float(), min_p.float(), uniforms.float(), dtype)
+    if update:
+        if state is not None and rows is not None:
+            penalty_state_add(state, rows, toks)
+        con_advance(cstate, crows, toks)
+    return toks

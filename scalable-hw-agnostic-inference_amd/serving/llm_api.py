@@ -3,7 +3,10 @@
 
   POST /generate  {"prompt": str, "max_new_tokens": int, "image"?: base64,
                    "temperature"?, "top_k"?, "top_p"?, "min_p"?, "repetition_penalty"?, "presence_penalty"?,
-                   "frequency_penalty"?, "seed"?, "logprobs"?: 0..20}
+                   "frequency_penalty"?, "seed"?, "logprobs"?: 0..20,
+                   "logit_bias"?: {"<token id>": -100..100}, "allowed_token_ids"?: [int], "min_tokens"?: int,
+                   "bad_words"?: [str], "bad_words_ids"?: [[int]], "guided_choice"?: [str],
+                   "guided_choice_ids"?: [[int]]}     (strings are tokenised without special tokens)
                   -> {"text": base64(utf-8 text), "execution_time": float,
                       "logprobs"?: [{"token", "logprob", "top_ids", "top_logprobs"}, ...]}   (only when asked)
   POST /benchmark {"n_runs": int, "max_new_tokens": int, "prompt": str}
@@ -48,7 +51,7 @@ import io
 import os
 import time
 import traceback
-from typing import Optional
+from typing import Dict, List, Optional
 
 from .common import METRICS, LatencyCollector, ServerEnv, b64text, base_app, latency_report, mount_ui
 
@@ -145,6 +148,15 @@ def create_app(service=None, env: Optional[ServerEnv] = None, tpc=None):
         frequency_penalty: Optional[float] = Field(None, ge=-2.0, le=2.0)
         seed: Optional[int] = None
         logprobs: Optional[int] = Field(None, ge=0, le=20)
+        # constraints (engines/constraints.py): OpenAI's logit_bias object, vLLM's allowed_token_ids / min_tokens /
+        # bad_words / guided_choice; the string forms need the service's tokenizer, the *_ids forms do not
+        logit_bias: Optional[Dict[str, float]] = None
+        allowed_token_ids: Optional[List[int]] = None
+        min_tokens: Optional[int] = Field(None, ge=0)
+        bad_words: Optional[List[str]] = None
+        bad_words_ids: Optional[List[List[int]]] = None
+        guided_choice: Optional[List[str]] = None
+        guided_choice_ids: Optional[List[List[int]]] = None
 
     SAMPLING_FIELDS = ("temperature", "top_k", "top_p", "min_p", "repetition_penalty", "presence_penalty",
                        "frequency_penalty", "seed", "logprobs")
@@ -162,12 +174,45 @@ def create_app(service=None, env: Optional[ServerEnv] = None, tpc=None):
     class GenerateBenchmarkResponse(BaseModel):
         report: str = Field(..., description="Benchmark report")
 
+    def tokenise(text, what):
+        tok = getattr(service, "tokenizer", None)
+        if tok is None or not hasattr(tok, "encode"):
+            raise HTTPException(status_code=422, detail=f"{what}: this service has no tokenizer, send {what}_ids")
+        try:
+            ids = tok.encode(text, add_special_tokens=False)
+        except TypeError:
+            ids = tok.encode(text)
+        ids = [int(i) for i in ids]
+        if not ids:
+            raise HTTPException(status_code=422, detail=f"{what}: {text!r} tokenises to nothing")
+        return ids
+
     def params(n, request=None):
         p = SamplingParams(temperature=temperature, top_k=50, top_p=0.9, max_tokens=max(1, int(n)))
         for name in SAMPLING_FIELDS if request is not None else ():
             v = getattr(request, name)
             if v is not None:
                 setattr(p, name, v)
+        if request is None:
+            return p
+        if request.logit_bias is not None:
+            try:
+                p.logit_bias = {int(k): float(v) for k, v in request.logit_bias.items()}
+            except ValueError:
+                raise HTTPException(status_code=422, detail="logit_bias keys must be token ids") from None
+        if request.allowed_token_ids is not None:
+            p.allowed_token_ids = list(request.allowed_token_ids)
+        if request.min_tokens is not None:
+            p.min_tokens = request.min_tokens
+        for field, strings, ids in (("bad_words_ids", request.bad_words, request.bad_words_ids),
+                                    ("guided_choice", request.guided_choice, request.guided_choice_ids)):
+            if strings is not None or ids is not None:
+                what = "bad_words" if field == "bad_words_ids" else "guided_choice"
+                setattr(p, field, [list(w) for w in ids or ()] + [tokenise(t, what) for t in strings or ()])
+        try:
+            p.validate()
+        except ValueError as e:
+            raise HTTPException(status_code=422, detail=str(e)) from None
         return p
 
     multimodal = bool(getattr(service, "multimodal", False))
@@ -179,7 +224,13 @@ def create_app(service=None, env: Optional[ServerEnv] = None, tpc=None):
             prompt = add_instruct(prompt, True)
             if not multimodal:
                 image = None  # text-only model: the image is validated and acknowledged, not attended to
-        text, secs, seq = service.generate_text(prompt, params(max_new_tokens, request), image=image)
+        p = params(max_new_tokens, request)
+        try:
+            text, secs, seq = service.generate_text(prompt, p, image=image)
+        except ValueError as e:   # constraints that do not compile against the vocabulary (ids out of range, ...)
+            if not p.constrained:
+                raise
+            raise HTTPException(status_code=422, detail=str(e)) from None
         if request is not None:
             return text, secs, seq
         return text, secs
@@ -216,6 +267,8 @@ def create_app(service=None, env: Optional[ServerEnv] = None, tpc=None):
             METRICS.request_done(env, total)
             lps = list(seq.logprobs) if request.logprobs is not None else None
             return GenerateResponse(text=b64text(text), execution_time=total, logprobs=lps)
+        except HTTPException:
+            raise
         except Exception as e:
             traceback.print_exc()
             raise HTTPException(status_code=500, detail=f"text serialization failed: {e}")

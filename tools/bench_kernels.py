@@ -5,7 +5,8 @@
 python tools/bench_kernels.py [--only gemm,conv,attn,norm] [--json out.json]
 (--only kv8: decode attention over bf16 vs fp8 KV caches, then prefill attention over an fp8 cache by the native
 and the widen route; SHAI_KV8_ROWS=decode|prefill keeps one of the two groups;
---only sampler: the fused sampler plain / penalised / penalised + logprobs at B = 64, alternating rounds)
+--only sampler: the fused sampler plain / penalised / penalised + logprobs / constrained at B = 64, alternating
+rounds)
 """
 import argparse
 import json
@@ -593,8 +594,9 @@ def bench_kv8_prefill(rows):
 
 def bench_sampler(rows):
     """Device time per call of the fused sampler at B = 64: the plain kernel, the penalised kernel (every row with a
-    state row: repetition / frequency / presence penalties and min_p) and penalised + token_logprobs (N = 5).  The
-    three variants alternate over SHAI_SAMPLER_ROUNDS (5) rounds of 32 graph-captured calls each; median, min and max
+    state row: repetition / frequency / presence penalties and min_p), penalised + token_logprobs (N = 5) and the
+    constrained kernel (the penalised rows, each with a 1-state program that allows half the vocabulary and holds 16
+    biases).  The variants alternate over SHAI_SAMPLER_ROUNDS (5) rounds of 32 graph-captured calls each; median, min and max
     of the rounds are reported."""
     import statistics
     B, rounds = 64, int(os.environ.get("SHAI_SAMPLER_ROUNDS", "5"))
@@ -625,6 +627,25 @@ def bench_sampler(rows):
             ops.token_logprobs(logits, out, 5, None, vals, ids)
 
         variants = {"plain": plain, "penalised": pen, "penalised+logprobs": pen_lp}
+        if hasattr(ops, "sample_constrained"):
+            from shai_amd.engines import constraints as cn
+            from types import SimpleNamespace
+            gc = torch.Generator().manual_seed(1)
+            allow = (torch.rand(V, generator=gc) < 0.5).nonzero().reshape(-1).tolist()
+            top = logits[0].float().topk(16).indices.tolist()      # biases on tokens that reach the candidates
+            prm = SimpleNamespace(logit_bias={t: 0.5 * (i % 5 - 2) for i, t in enumerate(top)},
+                                  allowed_token_ids=allow, bad_words_ids=None, min_tokens=0, guided_choice=None,
+                                  ignore_eos=True, max_tokens=16)
+            pool = cn.compile_program(prm, [], V).words.cuda()
+            cstate = torch.zeros(B, device="cuda", dtype=torch.int32)
+            prog = torch.zeros(B, device="cuda", dtype=torch.int32)
+            ban = torch.zeros(B, device="cuda", dtype=torch.int32)
+
+            def con():
+                ops.sample_constrained(logits, temps, topk, topp, u, out, state, srow, rep, freq, pres, minp, pool,
+                                       cstate, prog, srow, ban)
+
+            variants["constrained"] = con
         t = {k: [] for k in variants}
         for _ in range(rounds):
             for k, fn in variants.items():
@@ -632,7 +653,8 @@ def bench_sampler(rows):
         for k, xs in t.items():
             rows.append({"kernel": "sampler", "variant": k, "B": B, "V": V, "us": statistics.median(xs),
                          "us_min": min(xs), "us_max": max(xs), "x_plain": statistics.median(xs) /
-                         statistics.median(t["plain"])})
+                         statistics.median(t["plain"]), "x_penalised": statistics.median(xs) /
+                         statistics.median(t["penalised"])})
 
 
 def main():
