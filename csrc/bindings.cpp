@@ -85,7 +85,7 @@ std::string gemm_key(const shai::GemmArgs& g) {
   // library-eligible problems (plain GEMM, bias at most) race hipBLASLt in the tuner, so their winner must
   // not be reused by a same-shape problem with a fused epilogue (and vice versa): separate key class
   // a folded-LayerNorm GEMM (row_mr) runs only unsplit on v4: it tunes and caches apart from the plain problem
-  return std::string(buf) + (g.rms ? "|rms" : "") + (g.w_scale ? "|fp8w" : "") + (g.w_mx_scale ? "|mxfp4w" : "") + (g.row_mr ? "|ln" : "") +
+  return std::string(buf) + (g.rms ? "|rms" : "") + (g.w_scale ? "|fp8w" : "") + (g.w_mx_scale ? "|mxfp4w" : "") + (g.w_nf4_absmax ? "|nf4w" : "") + (g.row_mr ? "|ln" : "") +
          (g.w_slice_rows ? "|wslice" + std::to_string(g.w_slice_rows) : "") +
          // a broadcast residual races only the kernels that wrap it: its winner is kept apart from the plain problem's
          (g.res_rows ? "|rr" : "") +
@@ -236,6 +236,19 @@ void launch_skinny_fp4_choice(const shai::GemmArgs& g, const Tensor& like, int k
                  [&](float* ws) { shai::launch_skinny_fp4(g, ws, kg, fixup, stream()); });
 }
 
+// NF4 weights at M <= 64 (csrc/kernels/gemv_nf4.hip): the only kernel of such a problem; kSkinnyCfg / kSkinnyFixCfg
+// under the problem's own "|nf4w" key, as for MXFP4
+void launch_skinny_nf4_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
+  with_workspace(shai::skinny_nf4_workspace_bytes(g, kg), like,
+                 [&](float* ws) { shai::launch_skinny_nf4(g, ws, kg, fixup, stream()); });
+}
+
+// the heuristic K-group count of a skinny-only problem, by weight format
+int skinny_only_kgroups(const shai::GemmArgs& g) {
+  if (g.w_nf4_absmax != nullptr) return shai::skinny_nf4_kgroups(g);
+  return g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g);
+}
+
 // MXFP4 weights at M > 64 (csrc/kernels/gemm_fp4.hip): tile config x split count
 void launch_fp4_tile_choice(const shai::GemmArgs& g, const Tensor& like, int tile, int splits) {
   with_workspace(shai::gemm_fp4_workspace_bytes(g, splits), like,
@@ -274,6 +287,11 @@ void launch_lib(const shai::GemmArgs& g, const Tensor& like) {
 }
 
 void launch_choice(const shai::GemmArgs& g, const Tensor& like, Choice c) {
+  if (g.w_nf4_absmax != nullptr) {
+    SHAI_CHECK(shai::skinny_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 skinny kernel");
+    launch_skinny_nf4_choice(g, like, c.splits, c.cfg == kSkinnyFixCfg);
+    return;
+  }
   if (g.w_mx_scale != nullptr) {
     if (g.M > 64) {
       SHAI_CHECK(shai::gemm_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 tile kernel");
@@ -348,9 +366,15 @@ Choice tune(const shai::GemmArgs& g_real, const Tensor& like, bool skinny_only =
   g.C = reinterpret_cast<shai::bf16_t*>(scratch.data_ptr());
   g.ldc = n_out;
   g.batch_c = (long)g.M * n_out;
-  Choice def{kSkinnyCfg, g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g)};
+  Choice def{kSkinnyCfg, skinny_only_kgroups(g)};
   std::vector<Choice> cands;
-  if (g.w_mx_scale != nullptr && g.M > 64) {  // the fp4 tile kernel: every tile config x split count
+  if (g.w_nf4_absmax != nullptr) {  // the nf4 skinny kernel: its K-group counts in both split-K forms
+    skinny_only = true;
+    for (int kg = 1; kg <= shai::skinny_nf4_max_kgroups(g); kg *= 2) {
+      cands.push_back({kSkinnyCfg, kg});
+      if (kg > 1) cands.push_back({kSkinnyFixCfg, kg});
+    }
+  } else if (g.w_mx_scale != nullptr && g.M > 64) {  // the fp4 tile kernel: every tile config x split count
     skinny_only = true;
     def = fp4_tile_default(g);
     for (int t = 0; t < shai::gemm_fp4_num_tiles(); ++t)
@@ -392,7 +416,10 @@ Choice tune(const shai::GemmArgs& g_real, const Tensor& like, bool skinny_only =
   // Decode-shaped problems (M <= 64) stream weights that are NOT cache resident in a real decode step (the
   // model's weights are tens of GB; the MALL holds 256 MB): each timed launch runs behind a flush of the
   // Infinity Cache so the candidates are ranked by their HBM-streaming speed, not by a warm-cache replay.
-  const bool cold = g.M <= 64 && (long)g.N * g.K * (g.w_scale ? 2 : g.w_mx_scale ? 1 : 4) / 2 >= (4L << 20);
+  // (weight bytes: bf16 2, fp8 1, MXFP4 1 / 2 per weight; NF4 4.5 bits = 9 / 16)
+  const long w_bytes = g.w_nf4_absmax ? (long)g.N * g.K * 9 / 16
+                                      : (long)g.N * g.K * (g.w_scale ? 2 : g.w_mx_scale ? 1 : 4) / 2;
+  const bool cold = g.M <= 64 && w_bytes >= (4L << 20);
   for (const Choice& c : cands) {
     launch_choice(g, like, c);  // warm (also instantiates caches)
     float ms = 0.f;
@@ -436,7 +463,7 @@ void run_skinny(const shai::GemmArgs& g, const Tensor& like) {
       c = tune(g, like, true);
       store_choice(g, key, c);
     } else {
-      c = Choice{kSkinnyCfg, g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g)};
+      c = Choice{kSkinnyCfg, skinny_only_kgroups(g)};
     }
   }
   launch_choice(g, like, c);
@@ -997,6 +1024,72 @@ void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optiona
   else run_skinny(g, a);
 }
 
+// NF4 weights (ops.quantize_nf4): w uint8 [N, K / 2] (two codes per byte, even k in the low nibble), w_scale the fp32
+// block maxima tiled per 128-wide K step, [ceil(K / 128), N, 2].  Activations a [M, K] of M <= 64 rows on the skinny
+// kernel (gemv_nf4.hip); ops.linear dequantises for anything else.  force_cfg (tests / tools; < 0: tuned per shape):
+// 1000 = the heuristic K-group count with the separate fold, 1000 + kg = kg K groups folded by the separate kernel
+// (1001 = no split), 1100 + kg = kg K groups fixed up inside the launch (1 <= kg <= 64), as for MXFP4.
+void gemm_nf4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
+              const optional<Tensor>& residual, double alpha, double res_alpha, int64_t act, bool glu,
+              int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale) {
+  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(0) <= 64 && a.size(1) >= 64 && a.size(1) % 64 == 0,
+             "nf4 gemm: a must be a 2-D activation [1 <= M <= 64, K] with K % 64 == 0 (dequantize for larger M), got ",
+             a.sizes());
+  const long M = a.size(0), K = a.size(1);
+  SHAI_CHECK(w.is_cuda() && w.scalar_type() == at::kByte && w.dim() == 2 && w.is_contiguous() && w.size(1) * 2 == K &&
+                 reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+             "nf4 gemm: w must be a contiguous, 16-byte aligned uint8 [N, K / 2] matrix, got ", w.sizes(), " for K = ", K);
+  const long N = w.size(0);
+  SHAI_CHECK(w_scale.has_value(), "nf4 gemm: w_scale (the fp32 absmax of quantize_nf4) is required");
+  const Tensor& am = *w_scale;
+  SHAI_CHECK(am.is_cuda() && am.get_device() == w.get_device() && am.scalar_type() == at::kFloat &&
+                 am.is_contiguous() && am.dim() == 3 && am.size(0) == (K + 127) / 128 && am.size(1) == N &&
+                 am.size(2) == 2 && reinterpret_cast<uintptr_t>(am.data_ptr()) % 4 == 0,
+             "nf4 gemm: w_scale must be contiguous float32 [ceil(K / 128), N, 2], got ", am.sizes());
+  check_bf16(c, "c");
+  SHAI_CHECK(N % 2 == 0 && (!glu || N % 4 == 0), "nf4 gemm: N must be even (glu: N % 4 == 0)");
+  SHAI_CHECK(c.dim() == 2 && c.size(0) == M && c.size(1) == (glu ? N / 2 : N), "gemm output shape mismatch ", c.sizes());
+  shai::GemmArgs g{};
+  g.A = cptr(a);
+  g.W = reinterpret_cast<const shai::bf16_t*>(w.data_ptr());
+  g.w_nf4_absmax = am.data_ptr<float>();
+  g.C = mptr(c);
+  g.M = (int)M;
+  g.K = (int)K;
+  g.N = (int)N;
+  g.lda = a.stride(0);
+  g.ldw = K / 2;  // bytes
+  g.ldc = c.stride(0);
+  g.batch = 1;
+  if (bias) {
+    check_bf16(*bias, "bias");
+    SHAI_CHECK(bias->numel() == N, "bias size");
+    g.bias = cptr(*bias);
+  }
+  if (residual) {
+    check_bf16(*residual, "residual");
+    SHAI_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == c.size(1), "residual shape");
+    g.residual = cptr(*residual);
+    g.ldr = residual->stride(0);
+  }
+  g.alpha = alpha;
+  g.res_alpha = res_alpha;
+  g.act = act;
+  g.glu = glu;
+  if (rms_eps >= 0) {
+    g.rms = 1;
+    g.rms_eps = (float)rms_eps;
+  }
+  SHAI_CHECK(shai::skinny_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 skinny kernel");
+  SHAI_CHECK(force_cfg < 0 || (force_cfg >= kSkinnyCfg && force_cfg <= kSkinnyCfg + 64) ||
+                 (force_cfg > kSkinnyFixCfg && force_cfg <= kSkinnyFixCfg + 64),
+             "nf4 gemm: bad force_cfg ", force_cfg, ": 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
+  if (force_cfg > kSkinnyFixCfg) launch_choice(g, a, Choice{kSkinnyFixCfg, (int)(force_cfg - kSkinnyFixCfg)});
+  else if (force_cfg > kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, (int)(force_cfg - kSkinnyCfg)});
+  else if (force_cfg == kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, shai::skinny_nf4_kgroups(g)});
+  else run_skinny(g, a);
+}
+
 // a: [M, K] or [B, M, K]; w: [N, K] or [B, N, K]; c: [M, N'] or [B, M, N'] (N' = N or N/2 for glu)
 void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
           const optional<Tensor>& bias2d, int64_t rows_per_bias2d, const optional<Tensor>& residual, double alpha,
@@ -1006,12 +1099,18 @@ void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tens
           double ln_eps, int64_t w_slice_rows, int64_t res_rows) {
   check_rows(a, "a");
   SHAI_CHECK(res_rows == 0 || (residual.has_value() && a.dim() == 2 && !w_scale.has_value() &&
-                               w.scalar_type() != at::ScalarType::Float4_e2m1fn_x2),
+                               w.scalar_type() != at::ScalarType::Float4_e2m1fn_x2 && w.scalar_type() != at::kByte),
              "residual_rows: 2D bf16-weight GEMMs with a residual");
   if (w.scalar_type() == at::ScalarType::Float4_e2m1fn_x2) {
     SHAI_CHECK(!bias2d && !gate && !ln_mr && !ln_s && !gn_part && !ln_stats && w_slice_rows == 0,
                "mxfp4 gemm: bias / activation / GLU / residual / folded RMSNorm epilogues only");
     gemm_mxfp4(a, w, c, bias, residual, alpha, res_alpha, act, glu, force_cfg, rms_eps, w_scale);
+    return;
+  }
+  if (w.scalar_type() == at::kByte) {
+    SHAI_CHECK(!bias2d && !gate && !ln_mr && !ln_s && !gn_part && !ln_stats && w_slice_rows == 0,
+               "nf4 gemm: bias / activation / GLU / residual / folded RMSNorm epilogues only");
+    gemm_nf4(a, w, c, bias, residual, alpha, res_alpha, act, glu, force_cfg, rms_eps, w_scale);
     return;
   }
   if (w_scale.has_value()) {  // fp8 (e4m3) weights + fp32 per-row scale: skinny (decode-shaped) kernel only
@@ -2111,6 +2210,25 @@ void dequant_mxfp4(const Tensor& wq, const Tensor& scales, const Tensor& out) {
                              reinterpret_cast<const uint8_t*>(scales.data_ptr()), mptr(out), N, (int)K, stream());
 }
 
+// wq: uint8 [N, K / 2], absmax: fp32 [ceil(K / 128), N, 2] (ops.quantize_nf4) -> out bf16 [N, K]
+void dequant_nf4(const Tensor& wq, const Tensor& absmax, const Tensor& out) {
+  SHAI_CHECK(wq.is_cuda() && wq.scalar_type() == at::kByte && wq.dim() == 2 && wq.is_contiguous() &&
+                 wq.size(1) % 32 == 0 && reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0,
+             "dequant_nf4: wq must be a contiguous, 16-byte aligned uint8 [N, K / 2], K % 64 == 0");
+  const long N = wq.size(0), K = wq.size(1) * 2;
+  SHAI_CHECK(absmax.is_cuda() && absmax.get_device() == wq.get_device() && absmax.scalar_type() == at::kFloat &&
+                 absmax.is_contiguous() && absmax.dim() == 3 && absmax.size(0) == (K + 127) / 128 &&
+                 absmax.size(1) == N && absmax.size(2) == 2,
+             "dequant_nf4: absmax must be contiguous float32 [ceil(K / 128), N, 2], got ", absmax.sizes());
+  check_bf16(out, "out");
+  SHAI_CHECK(out.is_contiguous() && out.dim() == 2 && out.size(0) == N && out.size(1) == K &&
+                 out.get_device() == wq.get_device(),
+             "dequant_nf4: out must be a contiguous bf16 [N, K]");
+  SHAI_CHECK(K < (1L << 31), "dequant_nf4: K too large");
+  shai::launch_dequant_nf4(reinterpret_cast<const uint8_t*>(wq.data_ptr()), absmax.data_ptr<float>(), mptr(out), N,
+                           (int)K, stream());
+}
+
 // y = a w^T + bias + res_alpha residual into c, and LayerNorm(y) gamma + beta into c2, on the W-stationary kernel
 // (gemm_ws.hip: K = 320, N = 320, the row moments from the epilogue's registers).  Returns false (nothing launched)
 // when the problem is outside the kernel's contract; the caller then runs the GEMM and the norm separately.
@@ -2236,6 +2354,7 @@ TORCH_LIBRARY(shai, m) {
   m.def("gemm(Tensor a, Tensor w, Tensor(a!) c, Tensor? bias, Tensor? bias2d, int rows_per_bias2d, Tensor? residual, float alpha, float res_alpha, int act, bool glu, Tensor? gate=None, int rows_per_gate=1, int force_cfg=-1, float rms_eps=-1.0, Tensor? w_scale=None, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, int w_slice_rows=0, int res_rows=0) -> ()");
   m.def("dequant_fp8(Tensor w8, Tensor scale, Tensor(a!) out) -> ()");
   m.def("dequant_mxfp4(Tensor wq, Tensor scales, Tensor(a!) out) -> ()");
+  m.def("dequant_nf4(Tensor wq, Tensor absmax, Tensor(a!) out) -> ()");
   m.def("layernorm_mod(Tensor x, Tensor scale, Tensor shift, Tensor(a!) out, int rows_per_mod, float eps) -> ()");
   m.def("qk_norm_rope(Tensor(a!) x, Tensor? q_w, Tensor? k_w, Tensor? cos, Tensor? sin, int H, int D, int S, float eps) -> ()");
   m.def("conv2d(Tensor x, Tensor? x2, Tensor w, Tensor(a!) out, Tensor? bias, Tensor? bias2d, Tensor? residual, Tensor? in_scale, Tensor? in_shift, int in_act, int kh, int kw, int stride, int pad, bool upsample, int act, float res_alpha, Tensor? ln_mr=None, Tensor? ln_s=None, Tensor(b!)? gn_part=None, Tensor(c!)? ln_stats=None, float ln_eps=1e-5, bool up_phases=False, int res_rows=0) -> ()");
@@ -2288,6 +2407,7 @@ TORCH_LIBRARY_IMPL(shai, CUDA, m) {
   m.impl("gemm", &gemm);
   m.impl("dequant_fp8", &dequant_fp8);
   m.impl("dequant_mxfp4", &dequant_mxfp4);
+  m.impl("dequant_nf4", &dequant_nf4);
   m.impl("gemm_f8", &gemm_f8);
   m.impl("gemm_lnout", &gemm_lnout);
   m.impl("quant_rows_fp8", &quant_rows_fp8);

@@ -158,6 +158,10 @@ struct GemmArgs {
   // row stride of bias2d in elements; 0 = N (a contiguous [M / rows_per_bias2d, N] matrix).  A column slice of a wider
   // matrix (the batched time-embedding GEMM's output) is read in place by every kernel that takes bias2d.  (Appended)
   long bias2d_ld;
+  // NF4 weights (gemv_nf4.hip, M <= 64): W is 4-bit codes into the normal-float table [N, K / 2] bytes (ldw in BYTES),
+  // w_nf4_absmax the fp32 block maxima tiled per 128-wide K step, [ceil(K / 128), N, 2].  Every other kernel rejects
+  // such a problem.  (Appended)
+  const float* w_nf4_absmax;
 };
 __host__ __device__ inline long bias2d_stride(const GemmArgs& a) { return a.bias2d_ld > 0 ? a.bias2d_ld : a.N; }
 // the broadcast residual's host contract for a kernel of `tile` output rows per tile
@@ -172,8 +176,10 @@ inline bool tile_act_supported(const GemmArgs& a) {
   if (a.glu) return a.act == 1 || a.act == 2 || a.act == 3;      // ACT_SILU, ACT_GELU, ACT_GELU_TANH
   return true;
 }
-// the weights are not plain bf16 (fp8 rows or MXFP4): only the kernels written for the format take them
-inline bool quantized_w(const GemmArgs& a) { return a.w_scale != nullptr || a.w_mx_scale != nullptr; }
+// the weights are not plain bf16 (fp8 rows, MXFP4 or NF4): only the kernels written for the format take them
+inline bool quantized_w(const GemmArgs& a) {
+  return a.w_scale != nullptr || a.w_mx_scale != nullptr || a.w_nf4_absmax != nullptr;
+}
 void launch_dequant_fp8_rows(const uint8_t* w8, const float* scale, bf16_t* out, long N, int K, hipStream_t s);
 // fp8 e4m3 MFMA GEMM (gemm_f8.hip): C = epi(a_scale[m] w_scale[n] A8 W8^T); A8 / W8 are e4m3 bytes, lda / ldw in
 // bytes; cfg 0 = 256 x 128 tile, 1 = 128 x 128
@@ -258,6 +264,16 @@ size_t gemm_fp4_workspace_bytes(const GemmArgs& a, int splits);
 void launch_gemm_fp4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s);
 // MXFP4 codes [N, K / 2] + tiled scales [ceil(K / 128), N, 4] -> bf16 [N, K] (K % 32 == 0)
 void launch_dequant_mxfp4(const uint8_t* wq, const uint8_t* scales, bf16_t* out, long N, int K, hipStream_t s);
+// NF4 skinny kernel (gemv_nf4.hip): 128-row W tiles x 128-wide K steps (two blocks of 64), M <= 64,
+// GemmArgs::w_nf4_absmax set; split-K over kg workgroups per tile (ws of skinny_nf4_workspace_bytes), folded by
+// launch_splitk_epilogue or, fixup = true and a ticket slice available, inside the launch
+bool skinny_nf4_supported(const GemmArgs& a);
+int skinny_nf4_kgroups(const GemmArgs& a);       // heuristic K-group count
+int skinny_nf4_max_kgroups(const GemmArgs& a);   // largest K-group count worth trying (autotuner)
+size_t skinny_nf4_workspace_bytes(const GemmArgs& a, int kg);
+void launch_skinny_nf4(const GemmArgs& a, float* ws, int kg, bool fixup, hipStream_t s);
+// NF4 codes [N, K / 2] + tiled absmax [ceil(K / 128), N, 2] -> bf16 [N, K] (K % 64 == 0)
+void launch_dequant_nf4(const uint8_t* wq, const float* absmax, bf16_t* out, long N, int K, hipStream_t s);
 
 // ---------------------------------------------------------------- attention
 struct AttnArgs {

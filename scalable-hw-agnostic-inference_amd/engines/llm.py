@@ -698,6 +698,8 @@ class LLMEngine:
         # vLLM-style ``quantization: fp8``: fp8 e4m3 weights + per-row scales for every TP linear
         # (after the norm fold, which rescales weight columns); decode GEMMs stream half the bytes
         self.quantization = (quantization or "").lower() or None
+        if self.quantization in ("bitsandbytes", "bnb"):  # vLLM's name of the NF4 route
+            self.quantization = "nf4"
         if self.quantization == "fp8":
             from ..parallel.layers import quantize_fp8_
             quantize_fp8_(self.model)
@@ -705,9 +707,15 @@ class LLMEngine:
             # OCP MXFP4 weight-only (e2m1 codes + e8m0 scale per 32 along K): a quarter of the bf16 weight bytes
             from ..parallel.layers import quantize_mxfp4_
             quantize_mxfp4_(self.model)
+        elif self.quantization == "nf4":
+            # bitsandbytes NF4 weight-only (4-bit normal-float codes + an fp32 absmax per 64 along K, no double
+            # quantisation): 4.5 bits per weight, the numbers of the reference's load_in_4bit deployments
+            from ..parallel.layers import quantize_nf4_
+            quantize_nf4_(self.model)
         elif self.quantization not in (None, "none", "bf16"):
             raise ValueError(f"quantization={quantization!r}: supported: fp8 (weight-only e4m3), mxfp4 (weight-only "
-                             "e2m1 + e8m0 group scales) or none")
+                             "e2m1 + e8m0 group scales), nf4 / bitsandbytes / bnb (weight-only normal-float 4-bit + "
+                             "fp32 absmax per 64) or none")
         self.max_num_seqs = max_num_seqs
         self.max_model_len = min(max_model_len, cfg.max_position_embeddings)
         self.max_blocks = (self.max_model_len + KV_BLOCK - 1) // KV_BLOCK
@@ -1474,6 +1482,7 @@ def bench_decode_throughput(args, rank, world):
            "deepseek_r1_distill_70b": LlamaConfig.deepseek_r1_distill_70b}[name]()
     B, P, G = args.batch, args.prompt_len, args.gen_len
     quant = getattr(args, "quantization", None)
+    quant = "nf4" if (quant or "").lower() in ("nf4", "bitsandbytes", "bnb") else quant
     kvd = getattr(args, "kv_cache_dtype", None)
     eng = LLMEngine(cfg, device=f"cuda:{torch.cuda.current_device()}", max_num_seqs=max(B, 1),
                     max_model_len=P + G + 64, enable_prefix_caching=False, quantization=quant,
@@ -1511,10 +1520,12 @@ def bench_decode_throughput(args, rank, world):
         "metric": (f"{label} output tokens/sec (fp8 e4m3 weights, bf16 activations, continuous batching)"
                    if quant == "fp8" else
                    f"{label} output tokens/sec (MXFP4 weights, bf16 activations, continuous batching)"
-                   if quant == "mxfp4" else f"{label} output tokens/sec (bf16, continuous batching)"),
+                   if quant == "mxfp4" else
+                   f"{label} output tokens/sec (NF4 weights, bf16 activations, continuous batching)"
+                   if quant == "nf4" else f"{label} output tokens/sec (bf16, continuous batching)"),
         "value": round(toks / el, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(1000 * el / args.steps, 2), "higher_is_better": True,
-        "scaling": "strong" if replicas == 1 else "weak", "vs_baseline": None, "dtype": {"fp8": "fp8w-bf16a", "mxfp4": "mxfp4w-bf16a"}.get(quant, "bf16"),
+        "scaling": "strong" if replicas == 1 else "weak", "vs_baseline": None, "dtype": {"fp8": "fp8w-bf16a", "mxfp4": "mxfp4w-bf16a", "nf4": "nf4w-bf16a"}.get(quant, "bf16"),
         "data": "synthetic prompts, random-init weights",
         "config": {"model": f"{hf} (architecture)", "global_batch": B * replicas,
                    "seq_len": P + G, "prompt_len": P, "gen_len": G,

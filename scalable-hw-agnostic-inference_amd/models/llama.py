@@ -284,6 +284,8 @@ class LlamaForCausalLM(nn.Module):
                 raise RuntimeError("fold_norms after fp8 quantisation: fold first, then quantize_fp8_")
             if lin_w.dtype == torch.float4_e2m1fn_x2:
                 raise RuntimeError("fold_norms after MXFP4 quantisation: fold first, then quantize_mxfp4_")
+            if lin_w.dtype == torch.uint8:
+                raise RuntimeError("fold_norms after NF4 quantisation: fold first, then quantize_nf4_")
             lin_w.copy_((lin_w.float() * norm.weight.float()[None, :]).to(lin_w.dtype))
             norm.weight.fill_(1.0)
         for layer in self.layers:

@@ -20,12 +20,12 @@ import torch
 from .. import native
 from . import reference as ref
 from .reference import (ACT_GELU, ACT_GELU_TANH, ACT_NONE, ACT_QUICK_GELU, ACT_RELU, ACT_SILU, act_id, mxfp4_pack,
-                        mxfp4_unpack, quantize_mxfp4, pack_conv_weight, pack_up2_phase_weight, unpack_conv_weight)
+                        mxfp4_unpack, quantize_mxfp4, NF4_TABLE, nf4_pack, nf4_unpack, quantize_nf4, pack_conv_weight, pack_up2_phase_weight, unpack_conv_weight)
 
 __all__ = [
     "rmsnorm", "layernorm", "groupnorm_stats", "groupnorm_apply", "groupnorm", "linear", "conv2d", "attention",
     "paged_attention", "decode_attention", "kv_write", "rope", "rope_pairs", "gated_act", "bias_act", "sched_step",
-    "softmax_", "embedding", "token_feedback", "decode_attention_rope", "decode_attention_rope_qkv", "gemm_partials", "quantize_fp8_rows", "dequant_fp8", "quantize_mxfp4", "dequant_mxfp4", "mxfp4_pack", "mxfp4_unpack", "is_mxfp4", "quant_rows_fp8", "gemm_f8", "pack_conv_weight", "pack_up2_phase_weight", "linear_wslices", "unpack_conv_weight", "act_id", "ACT_NONE", "ACT_SILU", "ACT_GELU",
+    "softmax_", "embedding", "token_feedback", "decode_attention_rope", "decode_attention_rope_qkv", "gemm_partials", "quantize_fp8_rows", "dequant_fp8", "quantize_mxfp4", "dequant_mxfp4", "mxfp4_pack", "mxfp4_unpack", "is_mxfp4", "NF4_TABLE", "quantize_nf4", "dequant_nf4", "nf4_pack", "nf4_unpack", "is_nf4", "quant_rows_fp8", "gemm_f8", "pack_conv_weight", "pack_up2_phase_weight", "linear_wslices", "unpack_conv_weight", "act_id", "ACT_NONE", "ACT_SILU", "ACT_GELU",
     "ACT_GELU_TANH", "ACT_QUICK_GELU", "ACT_RELU", "decode_splits", "set_decode_wb",
     "paged_attention_varlen", "rope_qkv_cache", "quantize_kv_fp8", "dequant_kv_fp8", "kv_dequant_blocks",
     "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE", "resolve_kv_prefill", "KV_PREFILL_ROUTES",
@@ -203,6 +203,38 @@ def _mxfp4_route(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tenso
     return dequant_mxfp4(w, w_scale), None
 
 
+# ---- NF4 weight-only quantisation (the bitsandbytes 4-bit format; ``quantize_nf4``: a load-time transform in pure
+# torch, format and layout in ops/reference.py).  2-D ungated GEMMs of <= 64 rows stream the packed codes through the
+# skinny kernel (csrc/kernels/gemv_nf4.hip); more rows, gated / LayerNorm-folded / batched calls and the CPU dequantise
+# to bf16 first (a fused NF4 tile GEMM does not exist yet).
+def is_nf4(w: torch.Tensor) -> bool:
+    return w.dtype == torch.uint8
+
+
+def dequant_nf4(wq: torch.Tensor, absmax: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """NF4 codes [N, K / 2] + tiled absmax -> [N, K] (torch on the CPU, the native kernel on the GPU)."""
+    if not wq.is_cuda:
+        return ref.dequant_nf4(wq, absmax, dtype)
+    out = torch.empty(wq.shape[0], wq.shape[1] * 2, dtype=torch.bfloat16, device=wq.device)
+    _K().dequant_nf4(wq, absmax, out)
+    return out if dtype == torch.bfloat16 else out.to(dtype)
+
+
+def _nf4_route(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor], direct_ok: bool = True,
+               glu: bool = False):
+    """(w, w_scale) for a GEMM of ``x`` against NF4 weights: the packed pair where the nf4 skinny kernel takes the
+    problem (GPU, <= 64 flattened rows, N even -- whole column quads under GLU), else the dequantised bf16 matrix."""
+    if w_scale is None:
+        raise ValueError("NF4 weights need w_scale= (the absmax of quantize_nf4)")
+    K = x.shape[-1]
+    if w.shape[1] * 2 != K:
+        raise ValueError(f"NF4 weight {tuple(w.shape)} holds K = {w.shape[1] * 2}, the activation has K = {K}")
+    M = x.numel() // K
+    if direct_ok and _gpu(x) and 1 <= M <= 64 and w.shape[0] % (4 if glu else 2) == 0:
+        return w, w_scale
+    return dequant_nf4(w, w_scale), None
+
+
 # fp8 weights on problems of more than 64 rows (prefill): "w8a8" quantises the activation per row on the fly and
 # runs the fp8 MFMA GEMM (gemm_f8.hip); "dequant" widens the weights to bf16 and runs the bf16 GEMMs
 FP8_PREFILL = os.environ.get("SHAI_FP8_PREFILL", "w8a8")
@@ -263,10 +295,15 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     ``MXFP4_FUSED_MAX_ROWS``; ``MXFP4_PREFILL``); larger problems, a ``row_affine`` call and the CPU dequantise to bf16
     first.  force_cfg (tests / tools) then
     names an fp4 config: 1000 (+ kg) / 1100 + kg at <= 64 rows, 1300 + 32 * tile + splits above.
+    ``w`` of dtype uint8 is NF4 (``quantize_nf4``; ``w_scale`` its fp32 absmax): an ``x`` of <= 64 flattened rows on
+    the GPU (N even, N % 4 == 0 under GLU) streams the packed codes through the nf4 skinny kernel (force_cfg
+    1000 (+ kg) / 1100 + kg); everything else dequantises to bf16 first.
     """
     if is_mxfp4(w):
         w, w_scale = _mxfp4_route(x, w, w_scale, direct_ok=row_affine is None)
-    if w_scale is not None and not is_mxfp4(w):
+    elif is_nf4(w):
+        w, w_scale = _nf4_route(x, w, w_scale, direct_ok=row_affine is None, glu=glu)
+    if w_scale is not None and not is_mxfp4(w) and not is_nf4(w):
         M = x.numel() // x.shape[-1]
         K = x.shape[-1]
         if (_gpu(x) and M > 64 and FP8_PREFILL == "w8a8" and alpha == 1.0 and K % 16 == 0
@@ -300,7 +337,7 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     r2 = residual.reshape(-1, Nout) if residual is not None else None
     # (force_cfg names an fp4 config, or pins the kernel of a broadcast-residual problem for the tests)
     _K().gemm(x2, w, y, bias, None, 1, r2, float(alpha), float(res_alpha), act_id(act), bool(glu), None, 1,
-              int(force_cfg) if (is_mxfp4(w) or residual_rows) else -1,
+              int(force_cfg) if (is_mxfp4(w) or is_nf4(w) or residual_rows) else -1,
               float(rms_eps) if rms_eps is not None else -1.0, w_scale, None, None, None, None, 1e-5, 0,
               int(residual_rows))
     return y.view(*lead, Nout)
@@ -461,7 +498,8 @@ def gemm_into(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias=None, ac
     rms_eps >= 0: x is RMS-normalised first (unweighted; fold the gain into w).
     w_scale: fp8 e4m3 ``w`` with per-row scales (skinny kernel only, as in ``linear``), or the group scales of an
     MXFP4 ``w`` (2-D x without a gate: the fp4 skinny kernel at <= 64 rows, force_cfg 1000 (+ kg) / 1100 + kg as
-    below, the fp4 tile GEMM above, force_cfg 1300 + 32 * tile + splits; anything else dequantises first).
+    below, the fp4 tile GEMM above, force_cfg 1300 + 32 * tile + splits; anything else dequantises first), or the
+    absmax of an NF4 ``w`` (2-D x of <= 64 rows without a gate: the nf4 skinny kernel; anything else dequantises).
     force_cfg (tests / tools): a tile config index, 1000 (+ kg) = skinny kernel with a separate split-K fold,
     1100 + kg = skinny kernel reducing its K groups inside the launch, 2000 = hipBLASLt.
 
@@ -472,6 +510,10 @@ def gemm_into(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias=None, ac
         w, w_scale = _mxfp4_route(x, w, w_scale, direct_ok=x.dim() == 2 and gate is None)
         if w_scale is None and force_cfg >= 1000:
             force_cfg = -1  # the forced number named the fp4 kernel
+    elif is_nf4(w):
+        w, w_scale = _nf4_route(x, w, w_scale, direct_ok=x.dim() == 2 and gate is None, glu=glu)
+        if w_scale is None and force_cfg >= 1000:
+            force_cfg = -1  # the forced number named the nf4 kernel
     if not _gpu(x):
         if w_scale is not None:
             w = dequant_fp8(w, w_scale)

@@ -221,6 +221,74 @@ def dequant_mxfp4(wq: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) 
     return out.to(dtype)
 
 
+# ---- NF4 (the bitsandbytes 4-bit normal-float format): a 4-bit code into the 16-quantile table below and one fp32
+# absmax per 64 consecutive k of a row; 4.5 bits per weight.  Dequantised weight, the contract of every path:
+# bf16_rne(fp32(NF4_TABLE[code]) * fp32(absmax)).  Logical shapes: codes [N, K] in 0..15, absmax [N, K / 64].  The layout
+# the kernels stream (csrc/kernels/gemv_nf4.hip): codes two per byte (even k in the low nibble), uint8 [N, K / 2]
+# row-major, and the absmax tiled per 128-wide K step, fp32 [ceil(K / 128), N, 2] (a block past K / 64 holds 0).
+# bitsandbytes' double quantisation of the absmax values is not reproduced.
+NF4_BLOCK = 64
+NF4_TABLE = (-1.0, -0.6961928009986877, -0.5250730514526367, -0.39491748809814453, -0.28444138169288635,
+             -0.18477343022823334, -0.09105003625154495, 0.0, 0.07958029955625534, 0.16093020141124725,
+             0.24611230194568634, 0.33791524171829224, 0.44070982933044434, 0.5626170039176941, 0.7229568362236023,
+             1.0)
+
+
+def nf4_pack(codes: torch.Tensor, absmax: torch.Tensor):
+    """Layout helper: codes uint8 [N, K] in 0..15 + absmax fp32 [N, K / 64] (logical layout) ->
+    (wq uint8 [N, K / 2], absmax fp32 [ceil(K / 128), N, 2]) as the kernels read them."""
+    N, K = codes.shape
+    B = absmax.shape[1]
+    assert codes.dtype == torch.uint8 and absmax.dtype == torch.float32 and absmax.shape[0] == N
+    assert K == B * NF4_BLOCK, "one absmax per 64 codes"
+    steps = (B + 1) // 2
+    am = torch.zeros((N, steps * 2), dtype=torch.float32, device=codes.device)
+    am[:, :B] = absmax
+    tiled = am.view(N, steps, 2).permute(1, 0, 2).contiguous()
+    return (codes[:, 0::2] | (codes[:, 1::2] << 4)).contiguous(), tiled
+
+
+def nf4_unpack(wq: torch.Tensor, absmax: torch.Tensor):
+    """Inverse of ``nf4_pack``: (codes uint8 [N, K], absmax fp32 [N, K / 64])."""
+    N, K2 = wq.shape
+    B = K2 * 2 // NF4_BLOCK
+    assert wq.dtype == torch.uint8 and K2 * 2 == B * NF4_BLOCK, "nf4 codes must be uint8 [N, K / 2], K % 64 == 0"
+    assert absmax.dim() == 3 and absmax.shape[1] == N and absmax.shape[2] == 2 and absmax.shape[0] == (B + 1) // 2, \
+        f"nf4 absmax {tuple(absmax.shape)} does not belong to codes {tuple(wq.shape)}"
+    codes = torch.stack([wq & 15, wq >> 4], dim=-1).reshape(N, K2 * 2)
+    return codes, absmax.permute(1, 0, 2).reshape(N, -1)[:, :B].contiguous()
+
+
+def quantize_nf4(w: torch.Tensor):
+    """bitsandbytes NF4 quantisation of w [N, K] (K % 64 == 0) along K: per block of 64, absmax = max |w| in fp32 and
+    each element the nearest table entry of w / absmax (a tie takes the lower index); an all-zero block gets absmax 0
+    and code 7.  Returns ``nf4_pack``'s pair."""
+    if w.dim() != 2 or w.shape[1] == 0 or w.shape[1] % NF4_BLOCK != 0:
+        raise ValueError(f"quantize_nf4: w must be [N, K] with K % 64 == 0, got {tuple(w.shape)}")
+    N, K = w.shape
+    wf = w.float().reshape(N, K // NF4_BLOCK, NF4_BLOCK)
+    absmax = wf.abs().amax(dim=-1)
+    v = wf / absmax.clamp(min=torch.finfo(torch.float32).tiny)[..., None]
+    table = torch.tensor(NF4_TABLE, dtype=torch.float32, device=w.device)
+    # the entry whose bucket of (rounded) midpoints holds v, then its two neighbours by the distances themselves: a
+    # lower neighbour wins a tie, an upper one must be strictly nearer
+    code = torch.bucketize(v, (table[1:] + table[:-1]) / 2, right=False)
+    up, down = (code + 1).clamp(max=15), (code - 1).clamp(min=0)
+    code = torch.where((table[up] - v).abs() < (table[code] - v).abs(), up, code)
+    code = torch.where((table[down] - v).abs() <= (table[code] - v).abs(), down, code)
+    code = torch.where((absmax == 0)[..., None], torch.full_like(code, 7), code)
+    return nf4_pack(code.reshape(N, K).to(torch.uint8), absmax)
+
+
+def dequant_nf4(wq: torch.Tensor, absmax: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """Table decode of ``quantize_nf4``'s pair -> [N, K]: the fp32 product table[code] * absmax, rounded once."""
+    codes, am = nf4_unpack(wq, absmax)
+    N, K = codes.shape
+    table = torch.tensor(NF4_TABLE, dtype=torch.float32, device=codes.device)
+    out = table[codes.long()].view(N, -1, NF4_BLOCK) * am.float()[..., None]
+    return out.reshape(N, K).to(dtype)
+
+
 def gate_rows(y, gate, rows_per_gate):
     """y [..., M, N] * gate[(b*M + m) // rows_per_gate] (flattened row index)."""
     N = y.shape[-1]

@@ -44,6 +44,8 @@ class _ShardLoadMixin:
         if getattr(self, "weight_scale", None) is not None:
             if ops.is_mxfp4(self.weight):
                 raise RuntimeError("quantize_fp8_: the layer already holds MXFP4 weights")
+            if ops.is_nf4(self.weight):
+                raise RuntimeError("quantize_fp8_: the layer already holds NF4 weights")
             return
         w8, scale = ops.quantize_fp8_rows(self.weight.data)
         self.weight = nn.Parameter(w8, requires_grad=False)
@@ -55,6 +57,8 @@ class _ShardLoadMixin:
     # ones dequantise first.
     def quantize_mxfp4_(self) -> None:
         if getattr(self, "weight_scale", None) is not None:
+            if ops.is_nf4(self.weight):
+                raise RuntimeError("quantize_mxfp4_: the layer already holds NF4 weights")
             if not ops.is_mxfp4(self.weight):
                 raise RuntimeError("quantize_mxfp4_: the layer already holds fp8 weights")
             return
@@ -68,14 +72,34 @@ class _ShardLoadMixin:
         self.weight = nn.Parameter(wq, requires_grad=False)
         self.register_buffer("weight_scale", scales)
 
+    # ---- NF4 weight-only quantisation (``quantization: nf4`` / ``bitsandbytes``): the weight becomes packed 4-bit
+    # codes [N, K / 2] + an fp32 absmax per block of 64 (``ops.quantize_nf4``), quantised AFTER sharding (a block
+    # never straddles two ranks); decode GEMMs of <= 64 rows stream 4.5 bits per weight, larger ones dequantise.
+    def quantize_nf4_(self) -> None:
+        if getattr(self, "weight_scale", None) is not None:
+            if ops.is_mxfp4(self.weight):
+                raise RuntimeError("quantize_nf4_: the layer already holds MXFP4 weights")
+            if not ops.is_nf4(self.weight):
+                raise RuntimeError("quantize_nf4_: the layer already holds fp8 weights")
+            return
+        k = self.weight.shape[1]
+        if k % 64 != 0:
+            what = (f"row-parallel shard in_local = {k} (in_features {self.in_features} over {self.tp_size} ranks)"
+                    if isinstance(self, RowParallelLinear) else f"in_features = {k}")
+            raise ValueError(f"quantize_nf4_: {type(self).__name__} {what} is not a multiple of the NF4 block "
+                             "size 64")
+        wq, absmax = ops.quantize_nf4(self.weight.data)
+        self.weight = nn.Parameter(wq, requires_grad=False)
+        self.register_buffer("weight_scale", absmax)
+
     @property
     def w_scale(self):
         return getattr(self, "weight_scale", None)
 
     @property
     def _w_cols(self) -> int:
-        """K of this shard's weight (an MXFP4 weight packs two codes per element)."""
-        return self.weight.shape[1] * (2 if ops.is_mxfp4(self.weight) else 1)
+        """K of this shard's weight (an MXFP4 / NF4 weight packs two codes per element)."""
+        return self.weight.shape[1] * (2 if ops.is_mxfp4(self.weight) or ops.is_nf4(self.weight) else 1)
 
     def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
         for name, p in list(self._parameters.items()):
@@ -278,5 +302,22 @@ def quantize_mxfp4_(model: nn.Module) -> int:
     for m in model.modules():
         if isinstance(m, FP8_LAYER_TYPES) and id(m) not in skip:
             m.quantize_mxfp4_()
+            n += 1
+    return n
+
+
+@torch.no_grad()
+def quantize_nf4_(model: nn.Module) -> int:
+    """Quantise every TP linear layer of ``model`` to NF4 weights in place: the layer types and the ``no_fp8``
+    opt-out of ``quantize_fp8_`` (embeddings / LM head stay bf16).  Call after any weight transform (RMSNorm gain
+    folding) and after sharding.  Returns the number of layers visited (already-quantised ones are left alone)."""
+    n = 0
+    skip = set()
+    for m in model.modules():
+        if getattr(m, "no_fp8", False):
+            skip.update(id(c) for c in m.modules())
+    for m in model.modules():
+        if isinstance(m, FP8_LAYER_TYPES) and id(m) not in skip:
+            m.quantize_nf4_()
             n += 1
     return n

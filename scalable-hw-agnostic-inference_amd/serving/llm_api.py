@@ -21,7 +21,10 @@ variant's behaviour).  Engine kwargs come from a /vllm_config.yaml-style file
 (rounded to 64-token KV blocks), quantization (``fp8``: e4m3 weights + per-row
 scales, bf16 activations; ``mxfp4``: OCP MXFP4 weights -- e2m1 codes with one
 e8m0 scale per 32 inputs, quantised on load -- bf16 activations: the 4-bit
-deployment of the reference's bitsandbytes ``load_in_4bit`` models) and
+deployment of the reference's bitsandbytes ``load_in_4bit`` models on another
+number grid; ``nf4`` = ``bitsandbytes`` = ``bnb``: those models' own format --
+4-bit normal-float codes with one fp32 absmax per 64 inputs, quantised on load,
+no double quantisation -- bf16 activations) and
 kv_cache_dtype (``auto`` / ``bf16``, or ``fp8`` / ``fp8_e4m3``: OCP e4m3fn KV
 cache with scalar k/v scales -- half the KV bytes per decode step, twice the
 tokens per block pool; every TP rank reads the same file, so the relaunched

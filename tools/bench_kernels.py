@@ -203,8 +203,9 @@ def _bench_fp4_tile_rows(rows, M, N, K, ncopy, reps, a, src, run):
 def bench_fp4(rows):
     """MXFP4 GEMMs at more than 64 rows (M = 128 / 256 / 1024 / 4096: ``bench_fp4_tile_rows``; SHAI_FP4_M selects
     the row counts) and the
-    decode GEMMs of Mistral-7B and a 70B Llama at M = 1 / 16 / 64 with bf16, fp8 (e4m3 + row scales) and MXFP4
-    weights: the tuned ``ops.linear`` of each (replayed from a HIP graph), the three variants alternating inside
+    decode GEMMs of Mistral-7B and a 70B Llama at M = 1 / 16 / 64 with bf16, fp8 (e4m3 + row scales), MXFP4 and NF4
+    (4-bit codes + an fp32 absmax per 64: 4.5 bits per weight) weights: the tuned ``ops.linear`` of each (replayed
+    from a HIP graph), the variants alternating inside
     every repeat, as the median time, the spread of the repeats ((max - min) / median) and the weight bytes actually streamed over the time.
     Every variant rotates over enough weight copies to exceed the 256 MB Infinity Cache."""
     reps = int(os.environ.get("SHAI_FP4_REPS", "5"))
@@ -213,9 +214,11 @@ def bench_fp4(rows):
     if only:
         shapes = [shapes[int(i)] for i in only.split(",")]
     for N, K in shapes:
-        nbytes = {"bf16": N * K * 2, "fp8": N * K + N * 4, "fp4": N * K // 2 + N * K // 32}
+        glu = os.environ.get("SHAI_FP4_GLU", "0") == "1" and (N, K) == (28672, 4096)   # Mistral-7B gate_up_proj
+        nbytes = {"bf16": N * K * 2, "fp8": N * K + N * 4, "fp4": N * K // 2 + N * K // 32,
+                  "nf4": N * K // 2 + N * K // 16}
         ncopy = {v: max(2, min(160, (768 << 20) // b + 1)) for v, b in nbytes.items()}
-        wts = {"bf16": [], "fp8": [], "fp4": []}
+        wts = {"bf16": [], "fp8": [], "fp4": [], "nf4": []}
         for i in range(max(ncopy.values())):
             w = rnd(N, K) * 0.02
             if i < ncopy["bf16"]:
@@ -224,6 +227,8 @@ def bench_fp4(rows):
                 wts["fp8"].append(ops.quantize_fp8_rows(w))
             if i < ncopy["fp4"]:
                 wts["fp4"].append(ops.quantize_mxfp4(w))
+            if i < ncopy["nf4"]:
+                wts["nf4"].append(ops.quantize_nf4(w))
             del w
         ms = [int(m) for m in os.environ.get("SHAI_FP4_M", "1,16,64,128,256,1024,4096").split(",")]
         for M in [m for m in ms if m > 64]:
@@ -235,6 +240,8 @@ def bench_fp4(rows):
             def run(v):
                 it[v] = (it[v] + 1) % ncopy[v]
                 w, sc = wts[v][it[v]]
+                if glu:   # the gate / up projection as the model runs it: SwiGLU in the epilogue
+                    return ops.linear(a, w, w_scale=sc, act="silu", glu=True)
                 return ops.linear(a, w, w_scale=sc)
             for v in wts:   # tune outside the timing
                 run(v)
@@ -245,7 +252,7 @@ def bench_fp4(rows):
                 for v in wts:
                     n_it = ncopy[v] * ((31 + ncopy[v]) // ncopy[v])
                     ts[v].append(graph_time(lambda: run(v), iters=n_it, reps=2))
-            r = dict(op="decode_fp4", shape=f"{M}x{N}x{K}")
+            r = dict(op="decode_fp4_glu" if glu else "decode_fp4", shape=f"{M}x{N}x{K}")
             for v in wts:
                 t = sorted(ts[v])
                 med = t[len(t) // 2]
@@ -253,6 +260,8 @@ def bench_fp4(rows):
                 r[f"{v}_spread_pct"] = 100.0 * (t[-1] - t[0]) / med
                 r[f"{v}_TBps"] = nbytes[v] / med / 1e12
             r["fp4_vs_fp8"] = r["fp8_us"] / r["fp4_us"]
+            r["nf4_vs_fp4"] = r["fp4_us"] / r["nf4_us"]
+            r["nf4_vs_bf16"] = r["bf16_us"] / r["nf4_us"]
             rows.append(r)
             print("  ".join(f"{k}={x:.2f}" if isinstance(x, float) else f"{k}={x}" for k, x in r.items()), flush=True)
         del wts

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""LLM decode with bf16, fp8 and MXFP4 weights, one after another in fresh child processes (each run owns the GPU
+"""LLM decode with bf16, fp8, MXFP4 and NF4 weights, one after another in fresh child processes (each run owns the GPU
 and its own autotuner cache): ``bench_decode_throughput`` of engines/llm.py per variant, one JSON line each, with
 the resident weight bytes of the engine added.  The variant ``mxfp4_dequant`` is mxfp4 with
 ``SHAI_MXFP4_PREFILL=dequant`` (problems of more than 64 rows dequantise the weights per call, the route before the fp4
@@ -7,7 +7,7 @@ tile GEMM): ``--variants mxfp4,mxfp4_dequant --repeats 3 --batch 128`` alternate
 line per variant (median and spread of output tokens/s, TPOT and TTFT over the repeats).
 
 python tools/bench_mxfp4.py [--llm-model mistral_7b] [--batch 64] [--prompt-len 128] [--gen-len 128]
-                            [--steps 2] [--warmup 1] [--variants bf16,fp8,mxfp4] [--repeats 1]
+                            [--steps 2] [--warmup 1] [--variants bf16,fp8,mxfp4,nf4] [--repeats 1]
 """
 import argparse
 import json
@@ -50,7 +50,7 @@ def main():
     ap.add_argument("--gen-len", type=int, default=128)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--warmup", type=int, default=1)
-    ap.add_argument("--variants", default="bf16,fp8,mxfp4")
+    ap.add_argument("--variants", default="bf16,fp8,mxfp4,nf4")
     ap.add_argument("--repeats", type=int, default=1, help="runs per variant, the variants alternating")
     ap.add_argument("--timeout", type=int, default=900, help="seconds per variant")
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
@@ -60,7 +60,7 @@ def main():
         return 0
     rc = 0
     variants = a.variants.split(",")
-    assert all(v in ("bf16", "fp8", "mxfp4", "mxfp4_dequant") for v in variants), variants
+    assert all(v in ("bf16", "fp8", "mxfp4", "mxfp4_dequant", "nf4") for v in variants), variants
     results = {v: [] for v in variants}
     for v in [v for _ in range(max(1, a.repeats)) for v in variants]:
         env = dict(os.environ)
