@@ -255,7 +255,20 @@ void launch_fp4_tile_choice(const shai::GemmArgs& g, const Tensor& like, int til
                  [&](float* ws) { shai::launch_gemm_fp4(g, ws, tile, splits, stream()); });
 }
 
+// NF4 weights at M > 64 (csrc/kernels/gemm_nf4.hip): tile config x split count, the numbers of the MXFP4 tile GEMM
+// (kFp4TileCfg + 32 * tile, both kernels have the same two tiles) under the problem's own "|nf4w" key
+static_assert(kFp4TileCfg == 1300, "force_cfg 1300 + 32 * tile + splits names both 4-bit tile kernels");
+void launch_nf4_tile_choice(const shai::GemmArgs& g, const Tensor& like, int tile, int splits) {
+  with_workspace(shai::gemm_nf4_workspace_bytes(g, splits), like,
+                 [&](float* ws) { shai::launch_gemm_nf4(g, ws, tile, splits, stream()); });
+}
+
+// the heuristic choice of a 4-bit tile problem (M > 64), by weight format
 Choice fp4_tile_default(const shai::GemmArgs& g) {
+  if (g.w_nf4_absmax != nullptr) {
+    const int tile = shai::gemm_nf4_tile(g);
+    return Choice{kFp4TileCfg + 32 * tile, shai::gemm_nf4_splits(g, tile)};
+  }
   const int tile = shai::gemm_fp4_tile(g);
   return Choice{kFp4TileCfg + 32 * tile, shai::gemm_fp4_splits(g, tile)};
 }
@@ -288,6 +301,12 @@ void launch_lib(const shai::GemmArgs& g, const Tensor& like) {
 
 void launch_choice(const shai::GemmArgs& g, const Tensor& like, Choice c) {
   if (g.w_nf4_absmax != nullptr) {
+    if (g.M > 64) {
+      SHAI_CHECK(shai::gemm_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 tile kernel");
+      if (!is_fp4_tile(c.cfg)) c = fp4_tile_default(g);  // a choice of the skinny kernel filed under this key
+      launch_nf4_tile_choice(g, like, (c.cfg - kFp4TileCfg) / 32, c.splits);
+      return;
+    }
     SHAI_CHECK(shai::skinny_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 skinny kernel");
     launch_skinny_nf4_choice(g, like, c.splits, c.cfg == kSkinnyFixCfg);
     return;
@@ -368,7 +387,12 @@ Choice tune(const shai::GemmArgs& g_real, const Tensor& like, bool skinny_only =
   g.batch_c = (long)g.M * n_out;
   Choice def{kSkinnyCfg, skinny_only_kgroups(g)};
   std::vector<Choice> cands;
-  if (g.w_nf4_absmax != nullptr) {  // the nf4 skinny kernel: its K-group counts in both split-K forms
+  if (g.w_nf4_absmax != nullptr && g.M > 64) {  // the nf4 tile kernel: every tile config x split count
+    skinny_only = true;
+    def = fp4_tile_default(g);
+    for (int t = 0; t < shai::gemm_nf4_num_tiles(); ++t)
+      for (int sp = 1; sp <= shai::gemm_nf4_max_splits(g); sp *= 2) cands.push_back({kFp4TileCfg + 32 * t, sp});
+  } else if (g.w_nf4_absmax != nullptr) {  // the nf4 skinny kernel: its K-group counts in both split-K forms
     skinny_only = true;
     for (int kg = 1; kg <= shai::skinny_nf4_max_kgroups(g); kg *= 2) {
       cands.push_back({kSkinnyCfg, kg});
@@ -469,7 +493,7 @@ void run_skinny(const shai::GemmArgs& g, const Tensor& like) {
   launch_choice(g, like, c);
 }
 
-// MXFP4 problems of more than 64 rows: tuned over the fp4 tile kernel's configs x split counts (exact key, then the
+// MXFP4 / NF4 problems of more than 64 rows: tuned over their tile kernel's configs x split counts (exact key, then the
 // row-count bucket, as the bf16 prefill GEMMs); the heuristic choice under graph capture or with the tuner off.
 void run_fp4_tile(const shai::GemmArgs& g, const Tensor& like) {
   const std::string key = gemm_key(g);
@@ -1026,15 +1050,17 @@ void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optiona
 
 // NF4 weights (ops.quantize_nf4): w uint8 [N, K / 2] (two codes per byte, even k in the low nibble), w_scale the fp32
 // block maxima tiled per 128-wide K step, [ceil(K / 128), N, 2].  Activations a [M, K] of M <= 64 rows on the skinny
-// kernel (gemv_nf4.hip); ops.linear dequantises for anything else.  force_cfg (tests / tools; < 0: tuned per shape):
-// 1000 = the heuristic K-group count with the separate fold, 1000 + kg = kg K groups folded by the separate kernel
-// (1001 = no split), 1100 + kg = kg K groups fixed up inside the launch (1 <= kg <= 64), as for MXFP4.
+// kernel (gemv_nf4.hip), more rows on the tile kernel (gemm_nf4.hip; both apply a folded RMSNorm's rstd in fp32 in
+// their epilogue); ops.linear dequantises gated / LayerNorm-folded / batched calls.  force_cfg (tests / tools; < 0: tuned per
+// shape), M <= 64: 1000 = the heuristic K-group count with the separate fold, 1000 + kg = kg K groups folded by the
+// separate kernel (1001 = no split), 1100 + kg = kg K groups fixed up inside the launch (1 <= kg <= 64), as for MXFP4.
+// M > 64: 1300 + 32 * tile + splits (tile 0 = 128 x 128, 1 = 256 x 128; splits 1..16, 0 = the heuristic count).  A
+// number of the other row range is a "bad force_cfg" error.
 void gemm_nf4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
               const optional<Tensor>& residual, double alpha, double res_alpha, int64_t act, bool glu,
               int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale) {
-  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(0) <= 64 && a.size(1) >= 64 && a.size(1) % 64 == 0,
-             "nf4 gemm: a must be a 2-D activation [1 <= M <= 64, K] with K % 64 == 0 (dequantize for larger M), got ",
-             a.sizes());
+  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(1) >= 64 && a.size(1) % 64 == 0,
+             "nf4 gemm: a must be a 2-D activation [M >= 1, K] with K % 64 == 0, got ", a.sizes());
   const long M = a.size(0), K = a.size(1);
   SHAI_CHECK(w.is_cuda() && w.scalar_type() == at::kByte && w.dim() == 2 && w.is_contiguous() && w.size(1) * 2 == K &&
                  reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
@@ -1076,6 +1102,20 @@ void gemm_nf4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<
   g.res_alpha = res_alpha;
   g.act = act;
   g.glu = glu;
+  if (M > 64) {  // the tile kernel
+    const int ft = (int)(force_cfg - kFp4TileCfg) / 32, fs = (int)(force_cfg - kFp4TileCfg) % 32;
+    SHAI_CHECK(force_cfg < 0 || (force_cfg >= kFp4TileCfg && ft < shai::gemm_nf4_num_tiles() && fs <= 16),
+               "nf4 gemm: bad force_cfg ", force_cfg, " for M = ", M,
+               " > 64: 1300 + 32 * tile + splits (tile 0..", shai::gemm_nf4_num_tiles() - 1, ", splits 0..16)");
+    if (rms_eps >= 0) {  // folded RMSNorm: rstd in fp32 inside the tile kernel, as the skinny kernel has it
+      g.rms = 1;
+      g.rms_eps = (float)rms_eps;
+    }
+    SHAI_CHECK(shai::gemm_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 tile kernel");
+    if (force_cfg >= 0) launch_choice(g, a, Choice{kFp4TileCfg + 32 * ft, fs > 0 ? fs : shai::gemm_nf4_splits(g, ft)});
+    else run_fp4_tile(g, a);
+    return;
+  }
   if (rms_eps >= 0) {
     g.rms = 1;
     g.rms_eps = (float)rms_eps;
@@ -1083,7 +1123,7 @@ void gemm_nf4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<
   SHAI_CHECK(shai::skinny_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 skinny kernel");
   SHAI_CHECK(force_cfg < 0 || (force_cfg >= kSkinnyCfg && force_cfg <= kSkinnyCfg + 64) ||
                  (force_cfg > kSkinnyFixCfg && force_cfg <= kSkinnyFixCfg + 64),
-             "nf4 gemm: bad force_cfg ", force_cfg, ": 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
+             "nf4 gemm: bad force_cfg ", force_cfg, " for M = ", M, " <= 64: 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
   if (force_cfg > kSkinnyFixCfg) launch_choice(g, a, Choice{kSkinnyFixCfg, (int)(force_cfg - kSkinnyFixCfg)});
   else if (force_cfg > kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, (int)(force_cfg - kSkinnyCfg)});
   else if (force_cfg == kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, shai::skinny_nf4_kgroups(g)});

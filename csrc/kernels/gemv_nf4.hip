@@ -72,38 +72,7 @@
 
 namespace shai {
 
-// bitsandbytes' nf4 quant map
-#define SHAI_NF4_TABLE                                                                                              \
-  -1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,                  \
-      -0.18477343022823334f, -0.09105003625154495f, 0.0f, 0.07958029955625534f, 0.16093020141124725f,                \
-      0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f, 1.0f
-
-// TABLE[i & 15] from literals (a chain of selects: no memory load beside the counted DMA of the ring)
-__device__ __forceinline__ float nf4_table_entry(int i) {
-  constexpr float t[16] = {SHAI_NF4_TABLE};
-  float v = t[0];
-#pragma unroll
-  for (int e = 1; e < 16; ++e) v = (i & 15) == e ? t[e] : v;
-  return v;
-}
-
-// 8 NF4 codes (one dword, even k in the low nibbles) -> 8 bf16 = bf16_rne(TABLE[code] * absmax).  tab: this lane's
-// entry of the table spread over the wave (lane l holds TABLE[l & 15]); the gather reads lane (address >> 2) & 63,
-// whose low four bits are the code -- the two bits above them belong to the next code and pick one of four copies.
-__device__ __forceinline__ bf16x8 nf4x8_widen(uint32_t codes, float absmax, float tab) {
-  bf16x8 r;
-  const int t = __float_as_int(tab);
-  float v[8];  // the eight gathers first: one DS round trip for the dword, not one per pair
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const uint32_t addr = i == 0 ? codes << 2 : codes >> (4 * i - 2);
-    v[i] = __int_as_float(__builtin_amdgcn_ds_bpermute((int)addr, t));
-  }
-#pragma unroll
-  for (int i = 0; i < 8; ++i) r[i] = (__bf16)(v[i] * absmax);
-  return r;
-}
-
+// (the table, nf4_table_entry and nf4x8_widen: skinny_common.h, shared with gemm_nf4.hip)
 struct WNf4 {
   static constexpr int BK = 128, SLICES = 8;  // K per step (2 blocks of 64), its k16 slices
   static constexpr bool FOLD = true, QUAD_STORES = true;

@@ -158,7 +158,7 @@ struct GemmArgs {
   // row stride of bias2d in elements; 0 = N (a contiguous [M / rows_per_bias2d, N] matrix).  A column slice of a wider
   // matrix (the batched time-embedding GEMM's output) is read in place by every kernel that takes bias2d.  (Appended)
   long bias2d_ld;
-  // NF4 weights (gemv_nf4.hip, M <= 64): W is 4-bit codes into the normal-float table [N, K / 2] bytes (ldw in BYTES),
+  // NF4 weights (gemv_nf4.hip for M <= 64, gemm_nf4.hip above): W is 4-bit codes into the normal-float table [N, K / 2] bytes (ldw in BYTES),
   // w_nf4_absmax the fp32 block maxima tiled per 128-wide K step, [ceil(K / 128), N, 2].  Every other kernel rejects
   // such a problem.  (Appended)
   const float* w_nf4_absmax;
@@ -272,6 +272,17 @@ int skinny_nf4_kgroups(const GemmArgs& a);       // heuristic K-group count
 int skinny_nf4_max_kgroups(const GemmArgs& a);   // largest K-group count worth trying (autotuner)
 size_t skinny_nf4_workspace_bytes(const GemmArgs& a, int kg);
 void launch_skinny_nf4(const GemmArgs& a, float* ws, int kg, bool fixup, hipStream_t s);
+// NF4 tile GEMM (gemm_nf4.hip): M > 64, GemmArgs::w_nf4_absmax set, bf16 MFMA on codes widened in registers (waves
+// striped over N); bias / activation / GLU / residual / folded RMSNorm epilogues.
+// tile 0 = 128 x 128, 1 = 256 x 128; split-K over `splits` K groups (ws of gemm_nf4_workspace_bytes) folded by
+// launch_splitk_epilogue
+bool gemm_nf4_supported(const GemmArgs& a);
+int gemm_nf4_num_tiles();
+int gemm_nf4_tile(const GemmArgs& a);               // heuristic tile config
+int gemm_nf4_splits(const GemmArgs& a, int tile);   // heuristic split count of that tile
+int gemm_nf4_max_splits(const GemmArgs& a);         // largest split count worth trying (autotuner)
+size_t gemm_nf4_workspace_bytes(const GemmArgs& a, int splits);
+void launch_gemm_nf4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s);
 // NF4 codes [N, K / 2] + tiled absmax [ceil(K / 128), N, 2] -> bf16 [N, K] (K % 64 == 0)
 void launch_dequant_nf4(const uint8_t* wq, const float* absmax, bf16_t* out, long N, int K, hipStream_t s);
 

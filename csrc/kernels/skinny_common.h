@@ -4,7 +4,7 @@
 //
 //   * device primitives: buffer descriptor, the DMA zero-fill sentinel, fragment typedefs, the write-through (sc1)
 //     loads / stores and the arrival ticket of the in-launch split-K hand-off, the counted vmcnt wait, the pair / quad
-//     epilogues, the e8m0 scale and e2m1 widen of MXFP4;
+//     epilogues, the e8m0 scale and e2m1 widen of MXFP4, the table and ds_bpermute widen of NF4;
 //   * skinny_rows_kernel<Fmt, MB, GLU, ACT, RMS, STAGES>: the wide body.  Fmt (WBf16 in gemv2.hip, WMxfp4 in
 //     gemv_fp4.hip) says how a K step's bytes reach LDS and become bf16 fragments; ring, waits, folded RMSNorm,
 //     epilogues and the split-K fixup are written once here;
@@ -124,6 +124,38 @@ __device__ __forceinline__ bf16x8 fp4x8_widen(uint32_t codes, float scale) {
   const bf16x2 d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(codes, scale, 3);
   r[0] = a[0]; r[1] = a[1]; r[2] = b[0]; r[3] = b[1];
   r[4] = c[0]; r[5] = c[1]; r[6] = d[0]; r[7] = d[1];
+  return r;
+}
+
+// bitsandbytes' nf4 quant map
+#define SHAI_NF4_TABLE                                                                                              \
+  -1.0f, -0.6961928009986877f, -0.5250730514526367f, -0.39491748809814453f, -0.28444138169288635f,                  \
+      -0.18477343022823334f, -0.09105003625154495f, 0.0f, 0.07958029955625534f, 0.16093020141124725f,                \
+      0.24611230194568634f, 0.33791524171829224f, 0.44070982933044434f, 0.5626170039176941f, 0.7229568362236023f, 1.0f
+
+// TABLE[i & 15] from literals (a chain of selects: no memory load beside the counted DMA of the ring)
+__device__ __forceinline__ float nf4_table_entry(int i) {
+  constexpr float t[16] = {SHAI_NF4_TABLE};
+  float v = t[0];
+#pragma unroll
+  for (int e = 1; e < 16; ++e) v = (i & 15) == e ? t[e] : v;
+  return v;
+}
+
+// 8 NF4 codes (one dword, even k in the low nibbles) -> 8 bf16 = bf16_rne(TABLE[code] * absmax).  tab: this lane's
+// entry of the table spread over the wave (lane l holds TABLE[l & 15]); the gather reads lane (address >> 2) & 63,
+// whose low four bits are the code -- the two bits above them belong to the next code and pick one of four copies.
+__device__ __forceinline__ bf16x8 nf4x8_widen(uint32_t codes, float absmax, float tab) {
+  bf16x8 r;
+  const int t = __float_as_int(tab);
+  float v[8];  // the eight gathers first: one DS round trip for the dword, not one per pair
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const uint32_t addr = i == 0 ? codes << 2 : codes >> (4 * i - 2);
+    v[i] = __int_as_float(__builtin_amdgcn_ds_bpermute((int)addr, t));
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) r[i] = (__bf16)(v[i] * absmax);
   return r;
 }
 

@@ -205,8 +205,10 @@ def _mxfp4_route(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tenso
 
 # ---- NF4 weight-only quantisation (the bitsandbytes 4-bit format; ``quantize_nf4``: a load-time transform in pure
 # torch, format and layout in ops/reference.py).  2-D ungated GEMMs of <= 64 rows stream the packed codes through the
-# skinny kernel (csrc/kernels/gemv_nf4.hip); more rows, gated / LayerNorm-folded / batched calls and the CPU dequantise
-# to bf16 first (a fused NF4 tile GEMM does not exist yet).
+# skinny kernel (csrc/kernels/gemv_nf4.hip).  More rows dequantise to bf16 first by default (``NF4_PREFILL`` =
+# "dequant") or, with "fused", stream the packed codes through the nf4 tile GEMM (csrc/kernels/gemm_nf4.hip: codes
+# widened to bf16 in registers, bf16 MFMA -- the same bf16 weights, another summation order).  Gated / LayerNorm-folded /
+# batched calls and the CPU always dequantise.
 def is_nf4(w: torch.Tensor) -> bool:
     return w.dtype == torch.uint8
 
@@ -220,18 +222,30 @@ def dequant_nf4(wq: torch.Tensor, absmax: torch.Tensor, dtype=torch.bfloat16) ->
     return out if dtype == torch.bfloat16 else out.to(dtype)
 
 
+# NF4 weights on problems of more than 64 rows (prefill, mixed steps, decode above 64 sequences): "dequant" (the
+# default) widens the whole matrix to bf16 per call and runs the bf16 GEMMs; "fused" runs the nf4 tile GEMM
+NF4_PREFILL = os.environ.get("SHAI_NF4_PREFILL", "dequant")
+# largest row count the fused route takes (0: no cap): the largest measured M up to which it beats the dequantise
+# route by more than both spreads at every measured shape (profiles/nf4_prefill.md: 1.04-2.97x up to 512 rows, slower
+# at 6144 x 4096 from 768 rows and at every shape at 2048)
+NF4_FUSED_MAX_ROWS = int(os.environ.get("SHAI_NF4_FUSED_MAX_ROWS", "512"))
+
+
 def _nf4_route(x: torch.Tensor, w: torch.Tensor, w_scale: Optional[torch.Tensor], direct_ok: bool = True,
                glu: bool = False):
-    """(w, w_scale) for a GEMM of ``x`` against NF4 weights: the packed pair where the nf4 skinny kernel takes the
-    problem (GPU, <= 64 flattened rows, N even -- whole column quads under GLU), else the dequantised bf16 matrix."""
+    """(w, w_scale) for a GEMM of ``x`` against NF4 weights: the packed pair where an nf4 kernel takes the problem
+    (GPU, N even -- whole column quads under GLU; <= 64 flattened rows: the skinny kernel; more rows: the tile kernel
+    when ``NF4_PREFILL`` is "fused" and the row count is within ``NF4_FUSED_MAX_ROWS``), else the dequantised bf16
+    matrix."""
     if w_scale is None:
         raise ValueError("NF4 weights need w_scale= (the absmax of quantize_nf4)")
     K = x.shape[-1]
     if w.shape[1] * 2 != K:
         raise ValueError(f"NF4 weight {tuple(w.shape)} holds K = {w.shape[1] * 2}, the activation has K = {K}")
     M = x.numel() // K
-    if direct_ok and _gpu(x) and 1 <= M <= 64 and w.shape[0] % (4 if glu else 2) == 0:
-        return w, w_scale
+    if direct_ok and _gpu(x) and M >= 1 and w.shape[0] % (4 if glu else 2) == 0:
+        if M <= 64 or (NF4_PREFILL == "fused" and (NF4_FUSED_MAX_ROWS <= 0 or M <= NF4_FUSED_MAX_ROWS)):
+            return w, w_scale
     return dequant_nf4(w, w_scale), None
 
 
@@ -297,7 +311,8 @@ def linear(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None
     names an fp4 config: 1000 (+ kg) / 1100 + kg at <= 64 rows, 1300 + 32 * tile + splits above.
     ``w`` of dtype uint8 is NF4 (``quantize_nf4``; ``w_scale`` its fp32 absmax): an ``x`` of <= 64 flattened rows on
     the GPU (N even, N % 4 == 0 under GLU) streams the packed codes through the nf4 skinny kernel (force_cfg
-    1000 (+ kg) / 1100 + kg); everything else dequantises to bf16 first.
+    1000 (+ kg) / 1100 + kg); more rows do so through the nf4 tile GEMM (force_cfg 1300 + 32 * tile + splits) when
+    ``NF4_PREFILL`` is "fused" (up to ``NF4_FUSED_MAX_ROWS``); everything else dequantises to bf16 first.
     """
     if is_mxfp4(w):
         w, w_scale = _mxfp4_route(x, w, w_scale, direct_ok=row_affine is None)
@@ -499,7 +514,8 @@ def gemm_into(x: torch.Tensor, w: torch.Tensor, out: torch.Tensor, bias=None, ac
     w_scale: fp8 e4m3 ``w`` with per-row scales (skinny kernel only, as in ``linear``), or the group scales of an
     MXFP4 ``w`` (2-D x without a gate: the fp4 skinny kernel at <= 64 rows, force_cfg 1000 (+ kg) / 1100 + kg as
     below, the fp4 tile GEMM above, force_cfg 1300 + 32 * tile + splits; anything else dequantises first), or the
-    absmax of an NF4 ``w`` (2-D x of <= 64 rows without a gate: the nf4 skinny kernel; anything else dequantises).
+    absmax of an NF4 ``w`` (2-D x without a gate: the nf4 skinny kernel at <= 64 rows, the nf4 tile GEMM above when
+    ``NF4_PREFILL`` is "fused"; anything else dequantises).
     force_cfg (tests / tools): a tile config index, 1000 (+ kg) = skinny kernel with a separate split-K fold,
     1100 + kg = skinny kernel reducing its K groups inside the launch, 2000 = hipBLASLt.
 

@@ -160,22 +160,25 @@ def bench_fp4_tile_rows(rows, M, N, K, wts, ncopy, reps):
     (gemm_fp4.hip), same method as the decode rows (rotating weight copies, graph replay, the variants alternating
     inside every repeat, median and spread)."""
     a = rnd(M, K)
-    src = {"bf16": "bf16", "dequant": "fp4", "fused": "fp4"}
-    it = {v: 0 for v in src}
+    src = {"bf16": "bf16", "dequant": "fp4", "fused": "fp4", "nf4_dequant": "nf4", "nf4_fused": "nf4"}
+    it = {v: 0 for v in src}   # (nf4_*: the same two routes on NF4 weights, ``NF4_PREFILL``, gemm_nf4.hip)
+    nf4_default = ops.NF4_PREFILL
 
     def run(v):
         it[v] = (it[v] + 1) % ncopy[src[v]]
         w, sc = wts[src[v]][it[v]]
         ops.MXFP4_PREFILL = "dequant" if v == "dequant" else "fused"
+        ops.NF4_PREFILL = "fused" if v == "nf4_fused" else "dequant"
         try:
             return ops.linear(a, w, w_scale=sc)
         finally:
-            ops.MXFP4_PREFILL = "fused"
+            ops.MXFP4_PREFILL, ops.NF4_PREFILL = "fused", nf4_default
     cap, ops.MXFP4_FUSED_MAX_ROWS = ops.MXFP4_FUSED_MAX_ROWS, 0   # "fused" is the tile GEMM at every M: the row cap
-    try:                                                           # of the route is decided FROM this table
+    cap4, ops.NF4_FUSED_MAX_ROWS = ops.NF4_FUSED_MAX_ROWS, 0      # of the route is decided FROM this table
+    try:
         return _bench_fp4_tile_rows(rows, M, N, K, ncopy, reps, a, src, run)
     finally:
-        ops.MXFP4_FUSED_MAX_ROWS = cap
+        ops.MXFP4_FUSED_MAX_ROWS, ops.NF4_FUSED_MAX_ROWS = cap, cap4
 
 
 def _bench_fp4_tile_rows(rows, M, N, K, ncopy, reps, a, src, run):
@@ -196,6 +199,7 @@ def _bench_fp4_tile_rows(rows, M, N, K, ncopy, reps, a, src, run):
     r["fused_TFLOPs"] = 2.0 * M * N * K / (r["fused_us"] * 1e-6) / 1e12
     r["fused_vs_dequant"] = r["dequant_us"] / r["fused_us"]
     r["fused_vs_bf16"] = r["bf16_us"] / r["fused_us"]
+    r["nf4_fused_vs_dequant"] = r["nf4_dequant_us"] / r["nf4_fused_us"]
     rows.append(r)
     print("  ".join(f"{k}={x:.2f}" if isinstance(x, float) else f"{k}={x}" for k, x in r.items()), flush=True)
 

@@ -4,7 +4,8 @@ and its own autotuner cache): ``bench_decode_throughput`` of engines/llm.py per 
 the resident weight bytes of the engine added.  The variant ``mxfp4_dequant`` is mxfp4 with
 ``SHAI_MXFP4_PREFILL=dequant`` (problems of more than 64 rows dequantise the weights per call, the route before the fp4
 tile GEMM): ``--variants mxfp4,mxfp4_dequant --repeats 3 --batch 128`` alternates the two and ends with one summary
-line per variant (median and spread of output tokens/s, TPOT and TTFT over the repeats).
+line per variant (median and spread of output tokens/s, TPOT and TTFT over the repeats).  ``nf4_fused`` is nf4 with
+``SHAI_NF4_PREFILL=fused`` (the nf4 tile GEMM above 64 rows; plain ``nf4`` dequantises there).
 
 python tools/bench_mxfp4.py [--llm-model mistral_7b] [--batch 64] [--prompt-len 128] [--gen-len 128]
                             [--steps 2] [--warmup 1] [--variants bf16,fp8,mxfp4,nf4] [--repeats 1]
@@ -32,7 +33,8 @@ def child(a):
     llm.LLMEngine.__init__ = recording_init
     ns = argparse.Namespace(batch=a.batch, prompt_len=a.prompt_len, gen_len=a.gen_len, steps=a.steps,
                             warmup=a.warmup, tp=1, llm_model=a.llm_model,
-                            quantization={"bf16": None, "mxfp4_dequant": "mxfp4"}.get(a.child, a.child))
+                            quantization={"bf16": None, "mxfp4_dequant": "mxfp4", "nf4_fused": "nf4"}.get(a.child,
+                                                                                                         a.child))
     with torch.inference_mode():
         r = llm.bench_decode_throughput(ns, 0, 1)
     r["variant"] = a.child
@@ -60,10 +62,14 @@ def main():
         return 0
     rc = 0
     variants = a.variants.split(",")
-    assert all(v in ("bf16", "fp8", "mxfp4", "mxfp4_dequant", "nf4") for v in variants), variants
+    assert all(v in ("bf16", "fp8", "mxfp4", "mxfp4_dequant", "nf4", "nf4_fused") for v in variants), variants
     results = {v: [] for v in variants}
     for v in [v for _ in range(max(1, a.repeats)) for v in variants]:
         env = dict(os.environ)
+        if v == "nf4_fused":   # nf4 with the tile GEMM above 64 rows (gemm_nf4.hip); "nf4" is the default route
+            env["SHAI_NF4_PREFILL"] = "fused"
+        elif v == "nf4":
+            env.pop("SHAI_NF4_PREFILL", None)
         if v == "mxfp4_dequant":
             env["SHAI_MXFP4_PREFILL"] = "dequant"
         elif v == "mxfp4":
