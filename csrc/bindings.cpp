@@ -1976,7 +1976,7 @@ void kv_dequant_blocks(const Tensor& k_cache, const Tensor& v_cache, const Tenso
 }
 
 void sample(const Tensor& logits, const Tensor& temps, const Tensor& top_k, const Tensor& top_p,
-            const Tensor& uniforms, const Tensor& out) {
+            const Tensor& uniforms, const Tensor& out, bool full_vocab) {
   SHAI_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be a 2D GPU tensor");
   const bool bf16 = logits.scalar_type() == at::kBFloat16;
   SHAI_CHECK(bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or fp32");
@@ -1989,16 +1989,17 @@ void sample(const Tensor& logits, const Tensor& temps, const Tensor& top_k, cons
   SHAI_CHECK(temps.numel() == B && top_p.numel() == B && uniforms.numel() == B && top_k.numel() == B &&
                  out.numel() == B,
              "per-row parameter sizes");
-  shai::launch_sample(logits.data_ptr(), bf16, logits.stride(0), B, logits.size(1), temps.data_ptr<float>(),
-                      top_k.data_ptr<int>(), top_p.data_ptr<float>(), uniforms.data_ptr<float>(),
-                      out.data_ptr<int>(), stream());
+  // full_vocab: the launch whose rows pick their route themselves (top_k none or above 1024: the whole row)
+  const auto launch = full_vocab ? shai::launch_sample_full : shai::launch_sample;
+  launch(logits.data_ptr(), bf16, logits.stride(0), B, logits.size(1), temps.data_ptr<float>(),
+         top_k.data_ptr<int>(), top_p.data_ptr<float>(), uniforms.data_ptr<float>(), out.data_ptr<int>(), stream());
 }
 
 // the fused sampler with penalties and min_p (launch_sample_penalized): state [rows, V] int32 or none
 void sample_penalized(const Tensor& logits, const Tensor& temps, const Tensor& top_k, const Tensor& top_p,
                       const Tensor& uniforms, const Tensor& out, const optional<Tensor>& state,
                       const Tensor& state_rows, const Tensor& rep, const Tensor& freq, const Tensor& pres,
-                      const Tensor& min_p) {
+                      const Tensor& min_p, bool full_vocab) {
   SHAI_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be a 2D GPU tensor");
   const bool bf16 = logits.scalar_type() == at::kBFloat16;
   SHAI_CHECK(bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or fp32");
@@ -2026,10 +2027,11 @@ void sample_penalized(const Tensor& logits, const Tensor& temps, const Tensor& t
     st = state->data_ptr<int>();
     n_rows = state->size(0);
   }
-  shai::launch_sample_penalized(logits.data_ptr(), bf16, logits.stride(0), B, V, temps.data_ptr<float>(),
-                                top_k.data_ptr<int>(), top_p.data_ptr<float>(), uniforms.data_ptr<float>(),
-                                out.data_ptr<int>(), st, n_rows, state_rows.data_ptr<int>(), rep.data_ptr<float>(),
-                                freq.data_ptr<float>(), pres.data_ptr<float>(), min_p.data_ptr<float>(), stream());
+  const auto launch = full_vocab ? shai::launch_sample_penalized_full : shai::launch_sample_penalized;
+  launch(logits.data_ptr(), bf16, logits.stride(0), B, V, temps.data_ptr<float>(), top_k.data_ptr<int>(),
+         top_p.data_ptr<float>(), uniforms.data_ptr<float>(), out.data_ptr<int>(), st, n_rows,
+         state_rows.data_ptr<int>(), rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(),
+         min_p.data_ptr<float>(), stream());
 }
 
 // the fused sampler with constraint programs on top of the penalties (launch_sample_constrained): pool int32 [P]
@@ -2038,7 +2040,7 @@ void sample_constrained(const Tensor& logits, const Tensor& temps, const Tensor&
                         const Tensor& uniforms, const Tensor& out, const optional<Tensor>& state,
                         const Tensor& state_rows, const Tensor& rep, const Tensor& freq, const Tensor& pres,
                         const Tensor& min_p, const Tensor& pool, const Tensor& cstate, const Tensor& prog,
-                        const Tensor& slot, const Tensor& ban) {
+                        const Tensor& slot, const Tensor& ban, bool full_vocab) {
   SHAI_CHECK(logits.is_cuda() && logits.dim() == 2 && logits.stride(1) == 1, "logits must be a 2D GPU tensor");
   const bool bf16 = logits.scalar_type() == at::kBFloat16;
   SHAI_CHECK(bf16 || logits.scalar_type() == at::kFloat, "logits must be bf16 or fp32");
@@ -2074,13 +2076,13 @@ void sample_constrained(const Tensor& logits, const Tensor& temps, const Tensor&
     st = state->data_ptr<int>();
     n_rows = state->size(0);
   }
-  shai::launch_sample_constrained(logits.data_ptr(), bf16, logits.stride(0), B, V, temps.data_ptr<float>(),
-                                  top_k.data_ptr<int>(), top_p.data_ptr<float>(), uniforms.data_ptr<float>(),
-                                  out.data_ptr<int>(), st, n_rows, state_rows.data_ptr<int>(), rep.data_ptr<float>(),
-                                  freq.data_ptr<float>(), pres.data_ptr<float>(), min_p.data_ptr<float>(),
-                                  pool.numel() ? pool.data_ptr<int>() : nullptr, pool.numel(),
-                                  cstate.numel() ? cstate.data_ptr<int>() : nullptr, (int)cstate.numel(),
-                                  prog.data_ptr<int>(), slot.data_ptr<int>(), ban.data_ptr<int>(), stream());
+  const auto launch = full_vocab ? shai::launch_sample_constrained_full : shai::launch_sample_constrained;
+  launch(logits.data_ptr(), bf16, logits.stride(0), B, V, temps.data_ptr<float>(), top_k.data_ptr<int>(),
+         top_p.data_ptr<float>(), uniforms.data_ptr<float>(), out.data_ptr<int>(), st, n_rows,
+         state_rows.data_ptr<int>(), rep.data_ptr<float>(), freq.data_ptr<float>(), pres.data_ptr<float>(),
+         min_p.data_ptr<float>(), pool.numel() ? pool.data_ptr<int>() : nullptr, pool.numel(),
+         cstate.numel() ? cstate.data_ptr<int>() : nullptr, (int)cstate.numel(), prog.data_ptr<int>(),
+         slot.data_ptr<int>(), ban.data_ptr<int>(), stream());
 }
 
 void constraint_state_init(const Tensor& cstate, int64_t slot, int64_t value) {
@@ -2408,12 +2410,14 @@ TORCH_LIBRARY(shai, m) {
   m.def("bias_act(Tensor x, Tensor? bias, Tensor? residual, Tensor(a!) out, int act, float alpha) -> ()");
   m.def("rope(Tensor(a!) x, Tensor positions, Tensor cos, Tensor sin, int rot_dim, bool neox) -> ()");
   m.def("rope_pairs(Tensor(a!) x, Tensor cos, Tensor sin) -> ()");
-  m.def("sample(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out) -> ()");
+  m.def("sample(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out, "
+        "bool full_vocab=False) -> ()");
   m.def("sample_penalized(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out, "
-        "Tensor(b!)? state, Tensor state_rows, Tensor rep, Tensor freq, Tensor pres, Tensor min_p) -> ()");
+        "Tensor(b!)? state, Tensor state_rows, Tensor rep, Tensor freq, Tensor pres, Tensor min_p, "
+        "bool full_vocab=False) -> ()");
   m.def("sample_constrained(Tensor logits, Tensor temps, Tensor top_k, Tensor top_p, Tensor uniforms, Tensor(a!) out, "
         "Tensor(b!)? state, Tensor state_rows, Tensor rep, Tensor freq, Tensor pres, Tensor min_p, Tensor pool, "
-        "Tensor(c!) cstate, Tensor prog, Tensor slot, Tensor ban) -> ()");
+        "Tensor(c!) cstate, Tensor prog, Tensor slot, Tensor ban, bool full_vocab=False) -> ()");
   m.def("constraint_state_init(Tensor(a!) cstate, int slot, int value) -> ()");
   m.def("penalty_state_init(Tensor(a!) state, int row, Tensor tokens, int n_prompt) -> ()");
   m.def("token_logprobs(Tensor logits, Tensor tokens, Tensor? row_n, Tensor(a!) vals, Tensor(b!) ids) -> ()");

@@ -51,7 +51,9 @@ NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8",
               # the fp4 tile GEMM holds up to 128 accumulators beside the widened fragments: every instantiation
               "kernels/gemm_fp4.hip": "gemm_fp4_kernel",
               # the samplers (plain, penalised, constrained) and the log-probability kernel: every instantiation
-              "kernels/sampling.hip": ("sample_kernel", "sample_con_kernel", "token_logprobs_kernel"),
+              # (and their full-vocabulary forms)
+              "kernels/sampling.hip": ("sample_kernel", "sample_con_kernel", "token_logprobs_kernel",
+                                       "sample_full_kernel", "sample_con_full_kernel"),
               # the speculative verify attention holds the O^T accumulators of 32 query rows per wave: every form
               "kernels/attention_spec.hip": "spec_attn_kernel",
               # the NF4 skinny instantiations hold eight gathered fp32 table values beside the accumulators

@@ -439,6 +439,22 @@ void launch_sample_constrained(const void* logits, bool bf16, long ld, int B, in
                                int n_state_rows, const int* state_rows, const float* rep, const float* freq,
                                const float* pres, const float* min_p, const int* pool, long pool_words, int* cstate,
                                int n_slots, const int* prog, const int* slot, const int* ban, hipStream_t s);
+// The three samplers for batches with full-vocabulary rows (top_k <= 0, >= V or > 1024): same arguments, same rule.
+// Each row picks its route on the device: greedy rows and rows with 0 < top_k <= 1024 return the token the launch
+// above returns; the others are sampled exactly over every token (integer mass histograms: no sort, no scratch, and
+// a result that does not depend on the order of the atomics).
+void launch_sample_full(const void* logits, bool bf16, long ld, int B, int V, const float* temps, const int* top_k,
+                        const float* top_p, const float* uniforms, int* out, hipStream_t s);
+void launch_sample_penalized_full(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                                  const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                                  int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                                  const float* pres, const float* min_p, hipStream_t s);
+void launch_sample_constrained_full(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                                    const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                                    int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                                    const float* pres, const float* min_p, const int* pool, long pool_words,
+                                    int* cstate, int n_slots, const int* prog, const int* slot, const int* ban,
+                                    hipStream_t s);
 // cstate[slot] = value (one sequence's automaton state), in stream order.
 void launch_constraint_state_init(int* cstate, int n_slots, int slot, int value, hipStream_t s);
 // Clear one state row (V words) and scatter a token list into it: the first n_prompt tokens set the prompt flag, the

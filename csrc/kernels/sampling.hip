@@ -27,6 +27,10 @@
 // token (or the row bans its stop set).  Candidates at -inf are cut with min_p, so a masked token is never returned,
 // and the pick advances the row's state word (one thread, a binary search of the state's edge list) in the same
 // launch.  A row without a program takes exactly the penalised path.
+//
+// The full-vocabulary launches (launch_sample*_full, at the end of the file) take the same arguments and pick the
+// route per row: a top-k the candidate buffer holds runs the body above, anything else a sort-free walk of the whole
+// row (fv_pick).
 #include "common.h"
 #include "launchers.h"
 
@@ -605,6 +609,365 @@ void launch_token_logprobs(const void* logits, bool bf16, long ld, int B, int V,
                            int N, float* vals, int* ids, hipStream_t s) {
   if (bf16) token_logprobs_kernel<true><<<B, SMP_T, 0, s>>>(logits, ld, V, toks, row_n, N, vals, ids);
   else token_logprobs_kernel<false><<<B, SMP_T, 0, s>>>(logits, ld, V, toks, row_n, N, vals, ids);
+}
+
+// ---- full-vocabulary sampling: rows whose top-k is none (<= 0, >= V) or above SMP_MAXK, exact over every token, no
+// sort and no [V]-sized scratch.  The rule is sample_body's; what changes is how the sorted order is walked.  Every
+// element weighs m_i = trunc(exp((l_i - l_0) / T) * 2^40), an integer, so sums are exact and do not depend on the
+// order of the LDS atomics; elements below min_p or at -inf weigh nothing and enter no histogram (they are never
+// returned).  "How many candidates have a mass before them <= x" is then a radix descent over the order-preserving
+// keys whose buckets hold mass: walk the buckets from the top until the running mass would pass x, descend into that
+// bucket, and after the last digit one key is left, whose elements all weigh the same -- the position inside that tie
+// group is an integer division.  The nucleus cut is that question at x = top_p * total, the draw is it again at
+// x = u * kept mass, and the token is the tie of that rank in ascending index order.  A top-k in (SMP_MAXK, V) caps
+// the total by a count descent first (the same walk on counts).  Passes over the row: the maximum, the top digit's
+// histogram (shared by the descents), three (bf16 keys: one) more per descent, two for the tie.
+constexpr int FV_BITS = 40;   // 2^24 elements of weight <= 2^40 fit 64 bits
+
+__device__ __forceinline__ float key2f(uint32_t k) {
+  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
+}
+
+// how one row weighs its elements
+template <class Load>
+struct FvRow {
+  const Load& load;
+  int V;
+  float l0, inv_t, minp;
+  __device__ __forceinline__ float prob(float l) const { return __expf((l - l0) * inv_t); }
+  // (a function of the value alone: every element of a key weighs the same, in every pass)
+  __device__ __forceinline__ unsigned long long weight(float l) const {
+    return (unsigned long long)(prob(l) * (float)(1ull << FV_BITS));
+  }
+  // element i: its key and weight; false = dropped (below min_p, or masked)
+  __device__ __forceinline__ bool operator()(int i, uint32_t& key, unsigned long long& m) const {
+    const float l = load(i);
+    key = f2key(l);
+    m = weight(l);
+    return !(prob(l) < minp) && l > -INFINITY;
+  }
+};
+
+// where a descent stopped: the key, the count (count descents only) and mass of the kept elements that sort before
+// that key's first element, and the mass of the elements with that key
+struct FvCut {
+  uint32_t key, ca;
+  unsigned long long ma, m;
+};
+
+// the histogram storage: two mass copies per wave (by lane parity; logits crowd into a few exponent bins and
+// same-address LDS atomics of one wave instruction serialise).  A count descent adds all mass to copy 0 and counts
+// in copy 1's storage.
+typedef unsigned long long FvHist[2][256];
+
+// One digit's histogram over the kept elements whose key matches prefix under mask: tm[256] mass, tc[256] count
+// (COUNT only).  All SMP_T threads; ends with a barrier.
+template <bool COUNT, class Row>
+__device__ __forceinline__ void fv_hist(const Row& r, uint32_t mask, uint32_t prefix, int sh, FvHist* hm,
+                                        uint32_t* tc, unsigned long long* tm) {
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  for (int i = tid; i < SMP_WAVES * 2 * 256; i += SMP_T) (&hm[0][0][0])[i] = 0;
+  __syncthreads();
+  uint32_t* hc = reinterpret_cast<uint32_t*>(hm[w][1]);
+  for (int i = tid; i < r.V; i += SMP_T) {
+    uint32_t key;
+    unsigned long long m;
+    if (r(i, key, m) && (key & mask) == prefix) {
+      const int b = (key >> sh) & 255;
+      atomicAdd(&hm[w][COUNT ? 0 : lane & 1][b], m);
+      if constexpr (COUNT) atomicAdd(&hc[b], 1u);
+    }
+  }
+  __syncthreads();
+  if (tid < 256) {
+    unsigned long long s = 0;
+    uint32_t c = 0;
+#pragma unroll
+    for (int q = 0; q < SMP_WAVES; ++q) {
+      s += hm[q][0][tid];
+      if constexpr (COUNT) c += reinterpret_cast<const uint32_t*>(hm[q][1])[tid];
+      else s += hm[q][1][tid];
+    }
+    tm[tid] = s;
+    if constexpr (COUNT) tc[tid] = c;
+  }
+  __syncthreads();
+}
+
+// The descent.  COUNT: stop at the key that holds the x-th kept element (1 <= x <= kept elements).  Otherwise: at the
+// key that holds the last element whose mass before it is <= x (x < kept mass).  t0c / t0m: the top digit's
+// histogram.  The result is in *cut for every thread.
+template <bool KEY16, bool COUNT, class Row>
+__device__ __forceinline__ void fv_descend(const Row& r, unsigned long long x, FvHist* hm, const uint32_t* t0c,
+                                           const unsigned long long* t0m, uint32_t* tc, unsigned long long* tm,
+                                           FvCut* cut) {
+  const int tid = threadIdx.x;
+  if (tid == 0) cut->key = 0, cut->ca = 0, cut->ma = 0;
+  __syncthreads();
+  uint32_t mask = 0;
+  for (int pass = 3; pass >= (KEY16 ? 2 : 0); --pass) {
+    const int sh = 8 * pass;
+    const uint32_t* pc = t0c;
+    const unsigned long long* pm = t0m;
+    if (pass != 3) {
+      fv_hist<COUNT>(r, mask, cut->key, sh, hm, tc, tm);
+      pc = tc, pm = tm;
+    }
+    if (tid == 0) {
+      uint32_t ca = cut->ca;
+      unsigned long long ma = cut->ma;
+      int b = 255;
+      for (; b > 0; --b) {
+        if (COUNT ? ca + pc[b] >= x : ma + pm[b] > x) break;
+        if constexpr (COUNT) ca += pc[b];
+        ma += pm[b];
+      }
+      cut->ca = ca, cut->ma = ma, cut->m = pm[b];
+      cut->key |= (uint32_t)b << sh;
+    }
+    mask |= 255u << sh;
+    __syncthreads();
+  }
+  // (bf16: a negative value's key has its low 16 bits all ones, a positive value's all zeros)
+  if (KEY16 && tid == 0 && !(cut->key & 0x80000000u)) cut->key |= 0xFFFFu;
+  if (KEY16) __syncthreads();
+}
+
+// The rank-th (ascending index) element of load(0..V-1) whose key is thr; rank is clamped to the last one.  Wave w
+// owns chunk w of the row, as in smp_topk's tie selection.
+template <class Load>
+__device__ __forceinline__ int fv_nth_tie(const Load& load, int V, uint32_t thr, unsigned long long rank) {
+  __shared__ uint32_t tie_cnt[SMP_WAVES];
+  __shared__ int s_tok;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int C = ((V + SMP_WAVES - 1) / SMP_WAVES + 63) & ~63;
+  const int c0 = w * C, c1 = min(V, c0 + C);
+  uint32_t mine = 0;
+  for (int i0 = c0; i0 < c1; i0 += 64) {
+    const int i = i0 + lane;
+    mine += __popcll(__ballot(i < c1 && f2key(load(i)) == thr));
+  }
+  if (lane == 0) tie_cnt[w] = mine;
+  if (tid == 0) s_tok = -1;
+  __syncthreads();
+  uint32_t rank0 = 0, all = 0;
+  for (int q = 0; q < SMP_WAVES; ++q) {
+    if (q < w) rank0 += tie_cnt[q];
+    all += tie_cnt[q];
+  }
+  SHAI_DASSERT(rank < all);
+  const uint32_t want = all ? (uint32_t)min(rank, (unsigned long long)(all - 1)) : 0u;
+  for (int i0 = c0; i0 < c1 && rank0 <= want; i0 += 64) {
+    const int i = i0 + lane;
+    const bool eq = i < c1 && f2key(load(i)) == thr;
+    const unsigned long long bal = __ballot(eq);
+    if (eq && rank0 + __popcll(bal & ((1ull << lane) - 1ull)) == want) s_tok = i;
+    rank0 += __popcll(bal);
+  }
+  __syncthreads();
+  return s_tok;
+}
+
+// One full-vocabulary row: the token.  K: the row's top-k, SMP_MAXK < K <= V (V = no top-k); T > 0.
+template <bool KEY16, class Load>
+__device__ __forceinline__ int fv_pick(const Load& load, int V, int K, float T, float minp, float top_p, float u) {
+  __shared__ FvHist hm[SMP_WAVES];   // 64 KB
+  __shared__ unsigned long long t0m[256], tm[256];
+  __shared__ uint32_t t0c[256], tc[256];
+  __shared__ float red[SMP_WAVES];
+  __shared__ FvCut cut;
+  __shared__ unsigned long long s_total;
+  __shared__ uint32_t s_kept;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  SHAI_DASSERT(K > SMP_MAXK && K <= V && T > 0.f);
+  float mx = -INFINITY;
+  for (int i = tid; i < V; i += SMP_T) mx = fmaxf(mx, load(i));
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) red[w] = mx;
+  __syncthreads();
+  float l0 = red[0];
+#pragma unroll
+  for (int q = 1; q < SMP_WAVES; ++q) l0 = fmaxf(l0, red[q]);
+  // nothing but candidate 0 can stay (every token masked, or min_p above p_0 = 1): the first index of the maximum
+  if (!(l0 > -INFINITY) || minp > 1.f) return fv_nth_tie(load, V, f2key(l0), 0);
+  const FvRow<Load> r{load, V, l0, 1.f / T, minp};
+  const bool capped = K < V;
+  if (capped) fv_hist<true>(r, 0u, 0u, 24, hm, t0c, t0m);
+  else fv_hist<false>(r, 0u, 0u, 24, hm, t0c, t0m);
+  if (tid == 0) {
+    unsigned long long s = 0;
+    uint32_t c = 0;
+    for (int b = 0; b < 256; ++b) {
+      s += t0m[b];
+      if (capped) c += t0c[b];
+    }
+    s_total = s, s_kept = c;
+  }
+  __syncthreads();
+  // ---- the candidates' total: everything kept, or the first K of them
+  unsigned long long total = s_total;
+  if (capped && (uint32_t)K < s_kept) {
+    fv_descend<KEY16, true>(r, (unsigned long long)K, hm, t0c, t0m, tc, tm, &cut);
+    total = cut.ma + (unsigned long long)((uint32_t)K - cut.ca) * r.weight(key2f(cut.key));
+    __syncthreads();
+  }
+  // ---- nucleus: keep candidate i while the mass before it is <= top_p * total; kept = the mass of those
+  unsigned long long kept = total;
+  const double cd = fmax((double)top_p, 0.0) * (double)total;
+  if (top_p < 1.f && cd < (double)total) {
+    const unsigned long long x = min((unsigned long long)cd, total - 1);
+    fv_descend<KEY16, false>(r, x, hm, t0c, t0m, tc, tm, &cut);
+    const unsigned long long wt = r.weight(key2f(cut.key));
+    SHAI_DASSERT(wt > 0 && cut.m % wt == 0);
+    if (wt) kept = min(total, cut.ma + min(cut.m / wt, (x - cut.ma) / wt + 1) * wt);
+    __syncthreads();
+  }
+  // ---- draw: the candidate whose interval of the kept mass holds u * kept
+  const unsigned long long x = min((unsigned long long)(fmax((double)u, 0.0) * (double)kept), kept - 1);
+  fv_descend<KEY16, false>(r, x, hm, t0c, t0m, tc, tm, &cut);
+  const unsigned long long wt = r.weight(key2f(cut.key));
+  SHAI_DASSERT(wt > 0 && x >= cut.ma);
+  return fv_nth_tie(load, V, cut.key, wt ? (x - cut.ma) / wt : 0ull);
+}
+
+// The sampler body of a full-vocabulary launch.  The route is the row's own: greedy rows and rows with a top-k the
+// candidate buffer holds run sample_body, so their token does not depend on the launch they are in (and a captured
+// step never inspects top_k on the host); the others run fv_pick under the same load policy and bookkeeping.
+template <bool BF16, bool PEN, bool CON>
+__device__ __forceinline__ void sample_full_body(const void* __restrict__ logits, long ld, int V,
+                                                 const float* __restrict__ temps, const int* __restrict__ topk,
+                                                 const float* __restrict__ topp, const float* __restrict__ uniforms,
+                                                 int* __restrict__ out, const PenArgs& pa, const ConArgs& ca) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const float T = temps[row];
+  int K = topk[row];
+  if (K <= 0 || K > V) K = V;
+  if (T <= 0.f || K <= SMP_MAXK) {
+    sample_body<BF16, PEN, CON>(logits, ld, V, temps, topk, topp, uniforms, out, pa, ca);
+    return;
+  }
+  const char* base = reinterpret_cast<const char*>(logits) + (long)row * ld * (BF16 ? 2 : 4);
+  const float top_p = topp[row], u = uniforms[row];
+  int tok;
+  [[maybe_unused]] int* st = nullptr;     // as in sample_body: the row's state words, program, state and state word
+  [[maybe_unused]] ConProg cp{};
+  [[maybe_unused]] int cst = 0;
+  [[maybe_unused]] int* cslot = nullptr;
+  if constexpr (PEN) {
+    const int srow = pa.rows[row];
+    SHAI_DASSERT(srow < pa.n_rows);
+    if (pa.state && srow >= 0 && srow < pa.n_rows) st = pa.state + (long)srow * V;
+    const float minp = pa.minp[row];
+    const PenLoad<BF16> load{base, st, pa.rep[row], pa.freq[row], pa.pres[row]};
+    if constexpr (CON) {
+      __shared__ int s_bid[CON_MAX_BIAS];
+      __shared__ float s_bval[CON_MAX_BIAS];
+      const long off = ca.prog[row];
+      const int sl = ca.slot[row];
+      if (off >= 0) {
+        SHAI_DASSERT(sl >= 0 && sl < ca.n_slots);
+        if (ca.cstate && sl >= 0 && sl < ca.n_slots) {
+          cp = con_resolve(ca.pool, ca.pool_words, off, V);
+          cst = ca.cstate[sl];
+          SHAI_DASSERT(!cp.ok || (cst >= 0 && cst < cp.S));
+          if (cp.ok && (cst < 0 || cst >= cp.S)) cp.ok = false;
+          if (cp.ok) cslot = ca.cstate + sl;
+        }
+      }
+      if (cp.ok) {
+        for (int i = tid; i < cp.NB; i += SMP_T) {
+          s_bid[i] = cp.bid[i];
+          s_bval[i] = __int_as_float(cp.bval[i]);
+        }
+        __syncthreads();
+      }
+      const ConLoad<BF16> cload{load, cp.ok ? cp.masks + (long)cst * cp.W : nullptr,
+                                cp.ok && ca.ban[row] != 0 ? cp.stop : nullptr, cp.ok && cp.NB > 0 ? cp.plane : nullptr,
+                                s_bid, s_bval, cp.NB};
+      tok = fv_pick<false>(cload, V, K, T, minp, top_p, u);
+    } else {
+      tok = fv_pick<false>(load, V, K, T, minp, top_p, u);
+    }
+  } else {
+    const RawLoad<BF16> load{base};
+    tok = fv_pick<BF16>(load, V, K, T, 0.f, top_p, u);
+  }
+  if (tid != 0) return;
+  SHAI_DASSERT(tok >= 0 && tok < V);
+  tok = min(max(tok, 0), V - 1);
+  out[row] = tok;
+  // the pick's bookkeeping, as sample_body's: count the token in the penalty state, advance the automaton
+  if constexpr (PEN) {
+    if (st) atomicAdd(&st[tok], 1);
+  }
+  if constexpr (CON) {
+    if (cslot) {
+      int lo = cp.estart[cst], hi = cp.estart[cst + 1];
+      SHAI_DASSERT(lo >= 0 && lo <= hi && hi <= cp.E);
+      lo = max(lo, 0), hi = min(hi, cp.E);
+      const int end = hi;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (cp.etok[mid] < tok) lo = mid + 1;
+        else hi = mid;
+      }
+      int nx = lo < end && cp.etok[lo] == tok ? cp.enext[lo] : cp.dflt[cst];
+      SHAI_DASSERT(nx >= 0 && nx < cp.S);
+      if (nx < 0 || nx >= cp.S) nx = cst;
+      *cslot = nx;
+    }
+  }
+}
+
+template <bool BF16, bool PEN>
+__global__ void __launch_bounds__(SMP_T) sample_full_kernel(const void* __restrict__ logits, long ld, int V,
+                                                            const float* __restrict__ temps,
+                                                            const int* __restrict__ topk,
+                                                            const float* __restrict__ topp,
+                                                            const float* __restrict__ uniforms,
+                                                            int* __restrict__ out, PenArgs pa) {
+  sample_full_body<BF16, PEN, false>(logits, ld, V, temps, topk, topp, uniforms, out, pa, ConArgs{});
+}
+
+template <bool BF16>
+__global__ void __launch_bounds__(SMP_T) sample_con_full_kernel(const void* __restrict__ logits, long ld, int V,
+                                                                const float* __restrict__ temps,
+                                                                const int* __restrict__ topk,
+                                                                const float* __restrict__ topp,
+                                                                const float* __restrict__ uniforms,
+                                                                int* __restrict__ out, PenArgs pa, ConArgs ca) {
+  sample_full_body<BF16, true, true>(logits, ld, V, temps, topk, topp, uniforms, out, pa, ca);
+}
+
+void launch_sample_full(const void* logits, bool bf16, long ld, int B, int V, const float* temps, const int* top_k,
+                        const float* top_p, const float* uniforms, int* out, hipStream_t s) {
+  const PenArgs none{};
+  if (bf16)
+    sample_full_kernel<true, false><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, none);
+  else sample_full_kernel<false, false><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, none);
+}
+
+void launch_sample_penalized_full(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                                  const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                                  int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                                  const float* pres, const float* min_p, hipStream_t s) {
+  const PenArgs pa{state, n_state_rows, state_rows, rep, freq, pres, min_p};
+  if (bf16) sample_full_kernel<true, true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa);
+  else sample_full_kernel<false, true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa);
+}
+
+void launch_sample_constrained_full(const void* logits, bool bf16, long ld, int B, int V, const float* temps,
+                                    const int* top_k, const float* top_p, const float* uniforms, int* out, int* state,
+                                    int n_state_rows, const int* state_rows, const float* rep, const float* freq,
+                                    const float* pres, const float* min_p, const int* pool, long pool_words,
+                                    int* cstate, int n_slots, const int* prog, const int* slot, const int* ban,
+                                    hipStream_t s) {
+  const PenArgs pa{state, n_state_rows, state_rows, rep, freq, pres, min_p};
+  const ConArgs ca{pool, pool_words, cstate, n_slots, prog, slot, ban};
+  if (bf16)
+    sample_con_full_kernel<true><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa, ca);
+  else sample_con_full_kernel<false><<<B, SMP_T, 0, s>>>(logits, ld, V, temps, top_k, top_p, uniforms, out, pa, ca);
 }
 
 }  // namespace shai

@@ -180,19 +180,20 @@ def sample(logits: torch.Tensor, temps: torch.Tensor, top_k: torch.Tensor, top_p
     without it they come from ``gen``.  ``out`` (int32) receives the GPU sampler's tokens in place."""
     if all_greedy:
         return logits.float().argmax(-1)
-    if full_vocab is None:   # rows without a top-k in (0, 1024] sample over the whole vocabulary (torch path)
+    if full_vocab is None:   # rows without a top-k in (0, 1024] sample over the whole vocabulary
         full_vocab = bool(((top_k <= 0) | (top_k > ops.SAMPLER_MAX_K)).any()) if top_k.numel() else False
-    if (logits.is_cuda and logits.dim() == 2 and not full_vocab
+    if (logits.is_cuda and logits.dim() == 2 and (not full_vocab or ops.full_vocab_kernel())
             and os.environ.get("SHAI_TORCH_SAMPLER", "0") != "1"):
-        # fused on-device sampler (csrc/kernels/sampling.hip): top-k candidates (k <= 1024) -> top-p -> draw
+        # fused on-device sampler (csrc/kernels/sampling.hip): top-k candidates (k <= 1024) -> top-p -> draw, and
+        # with full_vocab its full-vocabulary launch (every row picks its route on the device)
         u = uniforms if uniforms is not None else torch.rand(logits.shape[0], device=logits.device, generator=gen)
         if out is not None:
             ops.sample(logits.contiguous(), temps.float().contiguous(), top_k.int().contiguous(),
-                       top_p.float().contiguous(), u, out)
+                       top_p.float().contiguous(), u, out, full_vocab=full_vocab)
             return out
         out = torch.empty(logits.shape[0], dtype=torch.int32, device=logits.device)
         ops.sample(logits.contiguous(), temps.float().contiguous(), top_k.int().contiguous(),
-                   top_p.float().contiguous(), u, out)
+                   top_p.float().contiguous(), u, out, full_vocab=full_vocab)
         return out.long()
     lf = logits.float()
     greedy = lf.argmax(-1)
@@ -436,10 +437,13 @@ class _DecodeGraph:
         self.pen, self.lp, self.con = pen, lp, con
         if pen or lp or con:
             self.NF = 18 if con else 15
-        # full_vocab: some row samples with top_k <= 0 (or > 1024) -- the fused sampler keeps 1024 candidates,
-        # so such steps publish the logits from the graph and sample them exactly over the whole vocabulary
-        # (torch top-k / top-p path, same inverse-CDF rule at the same uniforms) after the replay
+        # full_vocab: some row samples with top_k <= 0 (or > 1024) -- the step uses the sampler's full-vocabulary
+        # launch, inside the captured program like every other variant.  after_replay: with that kernel switched off
+        # (SHAI_FULL_VOCAB_SAMPLER=0, or SHAI_TORCH_SAMPLER=1) such steps publish the logits from the graph and
+        # sample them after the replay (torch top-k / top-p or the oracle, same rule at the same uniforms)
         self.full_vocab = full_vocab
+        self.after_replay = full_vocab and not (ops.full_vocab_kernel()
+                                                and os.environ.get("SHAI_TORCH_SAMPLER", "0") != "1")
         self.logits = None
         dev = engine.device
         mb = engine.max_blocks
@@ -501,15 +505,16 @@ class _DecodeGraph:
         eng = self.engine
         ops.token_feedback(self.ids, self.rowmap, eng.last_tokens)
         logits = eng.model(self.batch, eng.kv)
-        if self.full_vocab:
+        if self.after_replay:
             self.logits = logits
             return
         if self.greedy:
             self.toks.copy_(logits.float().argmax(-1))
         elif self.pen or self.con:
-            self._sample_pen(logits)
-        elif logits.is_cuda:   # full_vocab=False: no host-side inspection of the (captured) top-k values
-            sample(logits, self.temps, self.topk, self.topp, uniforms=self.u, out=self.toks, full_vocab=False)
+            self._sample_pen(logits, full_vocab=self.full_vocab)
+        elif logits.is_cuda:   # full_vocab from the graph's key: no host-side inspection of the (captured) top-k values
+            sample(logits, self.temps, self.topk, self.topp, uniforms=self.u, out=self.toks,
+                   full_vocab=self.full_vocab)
         else:
             self.toks.copy_(sample(logits, self.temps, self.topk, self.topp, uniforms=self.u))
         eng.last_tokens[:self.Bc].copy_(self.toks)
@@ -608,7 +613,7 @@ class _DecodeGraph:
         else:
             self._program()
         eng = self.engine
-        if self.full_vocab:   # exact full-vocabulary top-k / top-p at the same uniforms, outside the graph
+        if self.after_replay:   # exact full-vocabulary top-k / top-p at the same uniforms, outside the graph
             if self.pen or self.con:   # ... with penalties, min_p, constraints: the oracle's rule on the device, the
                 self._sample_pen(self.logits, full_vocab=True)   # states counted / advanced too
             else:
@@ -1487,7 +1492,9 @@ def bench_decode_throughput(args, rank, world):
     eng = LLMEngine(cfg, device=f"cuda:{torch.cuda.current_device()}", max_num_seqs=max(B, 1),
                     max_model_len=P + G + 64, enable_prefix_caching=False, quantization=quant,
                     kv_cache_dtype=kvd, kv_prefill=getattr(args, "kv_prefill", None))
-    params = SamplingParams(temperature=0.7, top_k=50, top_p=0.9, max_tokens=G, ignore_eos=True)
+    # (args.top_k: 0 makes every row a full-vocabulary row -- profiles/full_vocab_sampler.md)
+    params = SamplingParams(temperature=0.7, top_k=int(getattr(args, "top_k", 50)), top_p=0.9, max_tokens=G,
+                            ignore_eos=True)
     rng = np.random.default_rng(0)
     prompts = lambda: [rng.integers(10, cfg.vocab_size - 10, P).tolist() for _ in range(B)]
     for _ in range(max(1, args.warmup)):

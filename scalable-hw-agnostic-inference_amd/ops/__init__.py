@@ -898,9 +898,17 @@ def paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_
     return o
 
 
-# largest top-k the fused sampler keeps exactly (csrc/kernels/sampling.hip candidate buffer); rows asking for
-# more (or for no top-k at all, top_k <= 0) are sampled over the full vocabulary by the torch path
+# largest top-k the fused sampler's candidate buffer holds (csrc/kernels/sampling.hip); rows asking for more (or for
+# no top-k at all, top_k <= 0) are full-vocabulary rows: the ``full_vocab=True`` launches sample them exactly over
+# every token, sort-free, and the other rows of such a launch as the candidate-buffer launch does
 SAMPLER_MAX_K = 1024
+
+
+def full_vocab_kernel() -> bool:
+    """Whether full-vocabulary rows run the HIP sampler.  ``SHAI_FULL_VOCAB_SAMPLER=0`` restores the routes it
+    replaced (torch top-k / top-p for plain rows, ``ops.reference`` on the device for penalised and constrained
+    ones) for A/B runs."""
+    return os.environ.get("SHAI_FULL_VOCAB_SAMPLER", "1") != "0"
 
 
 def decode_splits(batch: int, hkv: int, max_ctx: int) -> int:
@@ -1074,9 +1082,10 @@ def rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, heads: int
     return qkv
 
 
-def sample(logits, temps, top_k, top_p, uniforms, out):
-    """Fused temperature / top-k / top-p sampling (GPU only; one workgroup per row)."""
-    _K().sample(logits, temps, top_k, top_p, uniforms, out)
+def sample(logits, temps, top_k, top_p, uniforms, out, full_vocab=False):
+    """Fused temperature / top-k / top-p sampling (GPU only; one workgroup per row).  ``full_vocab``: the launch for
+    batches with rows whose top_k is <= 0, >= V or above ``SAMPLER_MAX_K``; each row picks its route on the device."""
+    _K().sample(logits, temps, top_k, top_p, uniforms, out, bool(full_vocab))
     return out
 
 
@@ -1087,14 +1096,15 @@ def sample_penalized(logits, temps, top_k, top_p, uniforms, out, state, state_ro
                      full_vocab=False):
     """``sample`` with repetition / frequency / presence penalties and min_p, into ``out`` (int32).  ``state``:
     the [rows, V] int32 penalty-state table or None; ``state_rows[b]``: row b's state row, -1 for none.  The picked
-    tokens are counted in the state by the same call.  On the GPU one fused kernel (top_k <= 1024 candidates);
-    ``full_vocab`` (rows without such a top-k) and CPU tensors run the oracle (``reference.sample_penalized``)."""
-    if not _gpu(logits) or full_vocab:
+    tokens are counted in the state by the same call.  On the GPU one fused kernel; ``full_vocab`` (some row has no
+    top_k in 1..1024) its full-vocabulary launch.  CPU tensors run the oracle (``reference.sample_penalized``), and
+    so do full-vocabulary batches when :func:`full_vocab_kernel` is switched off."""
+    if not _gpu(logits) or (full_vocab and not full_vocab_kernel()):
         out.copy_(ref.sample_penalized(logits, temps, top_k, top_p, uniforms, state, state_rows, rep, freq, pres,
                                        min_p))
         return out
     _K().sample_penalized(logits.contiguous(), temps, top_k, top_p, uniforms, out, state, state_rows, rep, freq,
-                          pres, min_p)
+                          pres, min_p, bool(full_vocab))
     return out
 
 
@@ -1104,13 +1114,14 @@ def sample_constrained(logits, temps, top_k, top_p, uniforms, out, state, state_
     [P], the programs back to back; ``prog[b]``: word offset of row b's program, -1 = unconstrained (exactly the
     penalised path); ``cstate``: int32 [slots] automaton state words, ``slot[b]`` row b's; ``ban[b]`` != 0 removes the
     program's stop mask this step.  The same call counts the picked tokens in ``state`` and advances the state words.
-    On the GPU one fused kernel; ``full_vocab`` and CPU tensors run the oracle (``reference.sample_constrained``)."""
-    if not _gpu(logits) or full_vocab:
+    On the GPU one fused kernel, with ``full_vocab`` its full-vocabulary launch; CPU tensors (and full-vocabulary
+    batches with :func:`full_vocab_kernel` off) run the oracle (``reference.sample_constrained``)."""
+    if not _gpu(logits) or (full_vocab and not full_vocab_kernel()):
         out.copy_(ref.sample_constrained(logits, temps, top_k, top_p, uniforms, state, state_rows, rep, freq, pres,
                                          min_p, pool, cstate, prog, slot, ban))
         return out
     _K().sample_constrained(logits.contiguous(), temps, top_k, top_p, uniforms, out, state, state_rows, rep, freq,
-                            pres, min_p, pool, cstate, prog, slot, ban)
+                            pres, min_p, pool, cstate, prog, slot, ban, bool(full_vocab))
     return out
 
 

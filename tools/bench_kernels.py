@@ -6,7 +6,7 @@ python tools/bench_kernels.py [--only gemm,conv,attn,norm] [--json out.json]
 (--only kv8: decode attention over bf16 vs fp8 KV caches, then prefill attention over an fp8 cache by the native
 and the widen route; SHAI_KV8_ROWS=decode|prefill keeps one of the two groups;
 --only sampler: the fused sampler plain / penalised / penalised + logprobs / constrained at B = 64, alternating
-rounds)
+rounds; then its full-vocabulary launch (top_k = 0) beside the torch / oracle route it replaces)
 """
 import argparse
 import json
@@ -668,6 +668,54 @@ def bench_sampler(rows):
                          "us_min": min(xs), "us_max": max(xs), "x_plain": statistics.median(xs) /
                          statistics.median(t["plain"]), "x_penalised": statistics.median(xs) /
                          statistics.median(t["penalised"])})
+    bench_sampler_full(rows, rounds)
+
+
+def bench_sampler_full(rows, rounds):
+    """Full-vocabulary rows (top_k = 0) at top_p 0.9 and 1.0, B = 1 and 64: the HIP launch beside the route it
+    replaces -- engines.llm.sample's torch top-k / top-p for plain rows, ops.reference on the device for penalised
+    ones (SHAI_FULL_VOCAB_SAMPLER=0).  The replaced routes read the device on the host or allocate, so both sides
+    are timed eagerly with events (16 calls a round), alternating; median, min and max of the rounds."""
+    import statistics
+    from shai_amd.engines.llm import sample as engine_sample
+    for V in (32000, 128256):
+        for B in (1, 64):
+            g = torch.Generator(device="cuda").manual_seed(0)
+            logits = (torch.randn(B, V, device="cuda", generator=g) * 3).to(torch.bfloat16)
+            f32 = lambda v: torch.full((B,), v, device="cuda", dtype=torch.float32)
+            temps, u = f32(0.7), torch.rand(B, device="cuda", generator=g)
+            topk = torch.zeros(B, device="cuda", dtype=torch.int32)
+            out = torch.empty(B, device="cuda", dtype=torch.int32)
+            state = (torch.randint(1, 4, (B, V), device="cuda", generator=g) *
+                     (torch.rand(B, V, device="cuda", generator=g) < 0.10)).int()
+            srow = torch.arange(B, device="cuda", dtype=torch.int32)
+            rep, freq, pres, minp = f32(1.2), f32(0.3), f32(0.2), f32(0.05)
+            for tp in (0.9, 1.0):
+                topp = f32(tp)
+
+                def plain(on):
+                    os.environ["SHAI_FULL_VOCAB_SAMPLER"] = on
+                    engine_sample(logits, temps, topk, topp, uniforms=u, out=out if on == "1" else None,
+                                  full_vocab=True)
+
+                def pen(on):
+                    os.environ["SHAI_FULL_VOCAB_SAMPLER"] = on
+                    ops.sample_penalized(logits, temps, topk, topp, u, out, state, srow, rep, freq, pres, minp,
+                                         full_vocab=True)
+
+                variants = {"plain": plain, "penalised": pen}
+                t = {(k, on): [] for k in variants for on in "10"}
+                for _ in range(rounds):
+                    for (k, on), xs in t.items():
+                        xs.append(timeit(lambda: variants[k](on), iters=16, warmup=2) * 1e6)
+                os.environ.pop("SHAI_FULL_VOCAB_SAMPLER")
+                for k in variants:
+                    hip, old = t[k, "1"], t[k, "0"]
+                    rows.append({"kernel": "sampler_full", "variant": k, "B": B, "V": V, "top_p": tp,
+                                 "us": statistics.median(hip), "us_min": min(hip), "us_max": max(hip),
+                                 "replaced_us": statistics.median(old), "replaced_us_min": min(old),
+                                 "replaced_us_max": max(old),
+                                 "speedup": statistics.median(old) / statistics.median(hip)})
 
 
 def main():
