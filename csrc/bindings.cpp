@@ -187,11 +187,12 @@ constexpr int kSkinny2Cfg = 1200;
 constexpr int kSkinny2DeepCfg = 1250;
 inline bool is_skinny2(int cfg) { return cfg == kSkinny2Cfg || cfg == kSkinny2DeepCfg; }
 inline bool is_skinny(int cfg) { return cfg == kSkinnyCfg || cfg == kSkinnyFixCfg || is_skinny2(cfg); }
-// Choice.cfg of the MXFP4 tile GEMM (csrc/kernels/gemm_fp4.hip, M > 64): kFp4TileCfg + 32 * tile; Choice.splits = its
-// split-K count.  A forced number is kFp4TileCfg + 32 * tile + splits (splits 1..16, 0 = the heuristic count).
+// Choice.cfg of the 4-bit tile GEMMs (csrc/kernels/gemm_fp4.hip, gemm_nf4.hip, M > 64; both have the same two tiles):
+// kFp4TileCfg + 32 * tile; Choice.splits = its split-K count.  A forced number is kFp4TileCfg + 32 * tile + splits
+// (splits 1..16, 0 = the heuristic count).
 constexpr int kFp4TileCfg = 1300;
 inline bool is_fp4_tile(int cfg) {
-  return cfg >= kFp4TileCfg && cfg < kFp4TileCfg + 32 * shai::gemm_fp4_num_tiles() && (cfg - kFp4TileCfg) % 32 == 0;
+  return cfg >= kFp4TileCfg && cfg < kFp4TileCfg + 32 * shai::kQ4Tiles && (cfg - kFp4TileCfg) % 32 == 0;
 }
 
 // Last resort when neither the tuner nor the planner produced a usable config: an explicit, directly tested
@@ -229,48 +230,33 @@ void launch_skinny2_choice(const shai::GemmArgs& g, const Tensor& like, int kg, 
                  [&](float* ws) { shai::launch_skinny2(g, ws, kg, deep, stream()); });
 }
 
-// MXFP4 weights at M <= 64 (csrc/kernels/gemv_fp4.hip): the only kernel of such a problem.  Its choices reuse
-// kSkinnyCfg (split-K with the separate fold) and kSkinnyFixCfg (in-launch fixup) under the problem's own "|mxfp4w" key.
-void launch_skinny_fp4_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
-  with_workspace(shai::skinny_fp4_workspace_bytes(g, kg), like,
-                 [&](float* ws) { shai::launch_skinny_fp4(g, ws, kg, fixup, stream()); });
-}
-
-// NF4 weights at M <= 64 (csrc/kernels/gemv_nf4.hip): the only kernel of such a problem; kSkinnyCfg / kSkinnyFixCfg
-// under the problem's own "|nf4w" key, as for MXFP4
-void launch_skinny_nf4_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
-  with_workspace(shai::skinny_nf4_workspace_bytes(g, kg), like,
-                 [&](float* ws) { shai::launch_skinny_nf4(g, ws, kg, fixup, stream()); });
+// 4-bit weights (MXFP4 / NF4) at M <= 64 (csrc/kernels/gemv_fp4.hip, gemv_nf4.hip): the only kernel of such a
+// problem.  Its choices reuse kSkinnyCfg (split-K with the separate fold) and kSkinnyFixCfg (in-launch fixup) under the
+// problem's own "|mxfp4w" / "|nf4w" key.
+void launch_q4_skinny_choice(const shai::Q4Format& f, const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
+  with_workspace(f.skinny.workspace_bytes(g, kg), like,
+                 [&](float* ws) { f.skinny.launch(g, ws, kg, fixup, stream()); });
 }
 
 // the heuristic K-group count of a skinny-only problem, by weight format
 int skinny_only_kgroups(const shai::GemmArgs& g) {
-  if (g.w_nf4_absmax != nullptr) return shai::skinny_nf4_kgroups(g);
-  return g.w_mx_scale ? shai::skinny_fp4_kgroups(g) : shai::skinny_kgroups(g);
+  const shai::Q4Format* f = shai::q4_format(g);
+  return f != nullptr ? f->skinny.kgroups(g) : shai::skinny_kgroups(g);
 }
 
-// MXFP4 weights at M > 64 (csrc/kernels/gemm_fp4.hip): tile config x split count
-void launch_fp4_tile_choice(const shai::GemmArgs& g, const Tensor& like, int tile, int splits) {
-  with_workspace(shai::gemm_fp4_workspace_bytes(g, splits), like,
-                 [&](float* ws) { shai::launch_gemm_fp4(g, ws, tile, splits, stream()); });
-}
-
-// NF4 weights at M > 64 (csrc/kernels/gemm_nf4.hip): tile config x split count, the numbers of the MXFP4 tile GEMM
-// (kFp4TileCfg + 32 * tile, both kernels have the same two tiles) under the problem's own "|nf4w" key
+// 4-bit weights at M > 64 (csrc/kernels/gemm_fp4.hip, gemm_nf4.hip): tile config x split count, one set of numbers
+// (kFp4TileCfg + 32 * tile) under the problem's own key
 static_assert(kFp4TileCfg == 1300, "force_cfg 1300 + 32 * tile + splits names both 4-bit tile kernels");
-void launch_nf4_tile_choice(const shai::GemmArgs& g, const Tensor& like, int tile, int splits) {
-  with_workspace(shai::gemm_nf4_workspace_bytes(g, splits), like,
-                 [&](float* ws) { shai::launch_gemm_nf4(g, ws, tile, splits, stream()); });
+void launch_q4_tile_choice(const shai::Q4Format& f, const shai::GemmArgs& g, const Tensor& like, int tile, int splits) {
+  with_workspace(f.tile.workspace_bytes(g, splits), like,
+                 [&](float* ws) { f.tile.launch(g, ws, tile, splits, stream()); });
 }
 
-// the heuristic choice of a 4-bit tile problem (M > 64), by weight format
+// the heuristic choice of a 4-bit tile problem (M > 64)
 Choice fp4_tile_default(const shai::GemmArgs& g) {
-  if (g.w_nf4_absmax != nullptr) {
-    const int tile = shai::gemm_nf4_tile(g);
-    return Choice{kFp4TileCfg + 32 * tile, shai::gemm_nf4_splits(g, tile)};
-  }
-  const int tile = shai::gemm_fp4_tile(g);
-  return Choice{kFp4TileCfg + 32 * tile, shai::gemm_fp4_splits(g, tile)};
+  const shai::Q4TileOps& t = shai::q4_format(g)->tile;
+  const int tile = t.tile(g);
+  return Choice{kFp4TileCfg + 32 * tile, t.splits(g, tile)};
 }
 
 void launch_skinny_choice(const shai::GemmArgs& g, const Tensor& like, int kg, bool fixup) {
@@ -300,26 +286,15 @@ void launch_lib(const shai::GemmArgs& g, const Tensor& like) {
 }
 
 void launch_choice(const shai::GemmArgs& g, const Tensor& like, Choice c) {
-  if (g.w_nf4_absmax != nullptr) {
+  if (const shai::Q4Format* f = shai::q4_format(g)) {
     if (g.M > 64) {
-      SHAI_CHECK(shai::gemm_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 tile kernel");
-      if (!is_fp4_tile(c.cfg)) c = fp4_tile_default(g);  // a choice of the skinny kernel filed under this key
-      launch_nf4_tile_choice(g, like, (c.cfg - kFp4TileCfg) / 32, c.splits);
-      return;
-    }
-    SHAI_CHECK(shai::skinny_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 skinny kernel");
-    launch_skinny_nf4_choice(g, like, c.splits, c.cfg == kSkinnyFixCfg);
-    return;
-  }
-  if (g.w_mx_scale != nullptr) {
-    if (g.M > 64) {
-      SHAI_CHECK(shai::gemm_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 tile kernel");
+      SHAI_CHECK(f->tile.supported(g), f->name, " gemm: problem not supported by the ", f->kernel, " tile kernel");
       if (!is_fp4_tile(c.cfg)) c = fp4_tile_default(g);  // a choice of another kernel filed under this key
-      launch_fp4_tile_choice(g, like, (c.cfg - kFp4TileCfg) / 32, c.splits);
+      launch_q4_tile_choice(*f, g, like, (c.cfg - kFp4TileCfg) / 32, c.splits);
       return;
     }
-    SHAI_CHECK(shai::skinny_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 skinny kernel");
-    launch_skinny_fp4_choice(g, like, c.splits, c.cfg == kSkinnyFixCfg);
+    SHAI_CHECK(f->skinny.supported(g), f->name, " gemm: problem not supported by the ", f->kernel, " skinny kernel");
+    launch_q4_skinny_choice(*f, g, like, c.splits, c.cfg == kSkinnyFixCfg);
     return;
   }
   if (c.cfg == kLibCfg) {
@@ -387,27 +362,17 @@ Choice tune(const shai::GemmArgs& g_real, const Tensor& like, bool skinny_only =
   g.batch_c = (long)g.M * n_out;
   Choice def{kSkinnyCfg, skinny_only_kgroups(g)};
   std::vector<Choice> cands;
-  if (g.w_nf4_absmax != nullptr && g.M > 64) {  // the nf4 tile kernel: every tile config x split count
+  if (const shai::Q4Format* f = shai::q4_format(g)) {
     skinny_only = true;
-    def = fp4_tile_default(g);
-    for (int t = 0; t < shai::gemm_nf4_num_tiles(); ++t)
-      for (int sp = 1; sp <= shai::gemm_nf4_max_splits(g); sp *= 2) cands.push_back({kFp4TileCfg + 32 * t, sp});
-  } else if (g.w_nf4_absmax != nullptr) {  // the nf4 skinny kernel: its K-group counts in both split-K forms
-    skinny_only = true;
-    for (int kg = 1; kg <= shai::skinny_nf4_max_kgroups(g); kg *= 2) {
-      cands.push_back({kSkinnyCfg, kg});
-      if (kg > 1) cands.push_back({kSkinnyFixCfg, kg});
-    }
-  } else if (g.w_mx_scale != nullptr && g.M > 64) {  // the fp4 tile kernel: every tile config x split count
-    skinny_only = true;
-    def = fp4_tile_default(g);
-    for (int t = 0; t < shai::gemm_fp4_num_tiles(); ++t)
-      for (int sp = 1; sp <= shai::gemm_fp4_max_splits(g); sp *= 2) cands.push_back({kFp4TileCfg + 32 * t, sp});
-  } else if (g.w_mx_scale != nullptr) {
-    skinny_only = true;
-    for (int kg = 1; kg <= shai::skinny_fp4_max_kgroups(g); kg *= 2) {
-      cands.push_back({kSkinnyCfg, kg});
-      if (kg > 1) cands.push_back({kSkinnyFixCfg, kg});
+    if (g.M > 64) {  // the format's tile kernel: every tile config x split count
+      def = fp4_tile_default(g);
+      for (int t = 0; t < shai::kQ4Tiles; ++t)
+        for (int sp = 1; sp <= f->tile.max_splits(g); sp *= 2) cands.push_back({kFp4TileCfg + 32 * t, sp});
+    } else {  // the format's skinny kernel: its K-group counts in both split-K forms
+      for (int kg = 1; kg <= f->skinny.max_kgroups(g); kg *= 2) {
+        cands.push_back({kSkinnyCfg, kg});
+        if (kg > 1) cands.push_back({kSkinnyFixCfg, kg});
+      }
     }
   }
   if (!skinny_only) {
@@ -952,39 +917,52 @@ void attach_norm_io(shai::GemmArgs& g, const optional<Tensor>& ln_mr, const opti
   }
 }
 
-// MXFP4 weights (ops.quantize_mxfp4): w float4_e2m1fn_x2 [N, K / 2] (two codes per byte), w_scale e8m0 bytes tiled per
-// 128-wide K step, [ceil(K / 128), N, 4].  Activations a [M, K] of M <= 64 rows run on the skinny kernel
-// (gemv_fp4.hip), more rows on the tile kernel (gemm_fp4.hip; a folded RMSNorm runs as an explicit row-norm pass first).
+// 4-bit weights, format f (w.scalar_type() selects it in gemm()):
+//   MXFP4 (ops.quantize_mxfp4): w float4_e2m1fn_x2 [N, K / 2] (two codes per byte), w_scale e8m0 bytes tiled per
+//   128-wide K step, [ceil(K / 128), N, 4];
+//   NF4 (ops.quantize_nf4): w uint8 [N, K / 2] (two codes per byte, even k in the low nibble), w_scale the fp32 block
+//   maxima tiled per 128-wide K step, [ceil(K / 128), N, 2]; ops.linear dequantises gated / LayerNorm-folded / batched
+//   calls.
+// Activations a [M, K] of M <= 64 rows run on the format's skinny kernel (gemv_fp4.hip / gemv_nf4.hip), more rows on its
+// tile kernel (gemm_fp4.hip / gemm_nf4.hip).  A folded RMSNorm: the skinny kernels and the NF4 tile kernel apply rstd in
+// fp32 in their epilogue; above 64 rows MXFP4 runs an explicit row-norm pass first.
 // force_cfg (tests / tools; < 0: tuned per shape), M <= 64: 1000 = the heuristic K-group count with the separate fold,
 // 1000 + kg = kg K groups folded by the separate kernel (1001 = no split), 1100 + kg = kg K groups fixed up inside
-// the launch -- the numbers of the bf16 / fp8 skinny kernel, here always on gemv_fp4.hip (1 <= kg <= 64).  M > 64:
+// the launch -- the numbers of the bf16 / fp8 skinny kernel, here always on the format's own (1 <= kg <= 64).  M > 64:
 // 1300 + 32 * tile + splits (tile 0 = 128 x 128, 1 = 256 x 128; splits 1..16, 0 = the heuristic count).  A number
 // of the other row range is a "bad force_cfg" error.
-void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
-                const optional<Tensor>& residual, double alpha, double res_alpha, int64_t act, bool glu,
-                int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale) {
-  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(1) >= 32 && a.size(1) % 32 == 0,
-             "mxfp4 gemm: a must be a 2-D activation [M >= 1, K] with K % 32 == 0");
+void gemm_q4(const shai::Q4Format& f, const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
+             const optional<Tensor>& residual, double alpha, double res_alpha, int64_t act, bool glu,
+             int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale) {
+  const bool nf4 = &f == &shai::kNf4;
+  const int km = f.k_multiple;
+  // (the NF4 texts name the offending sizes)
+  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(1) >= km && a.size(1) % km == 0, f.name,
+             " gemm: a must be a 2-D activation [M >= 1, K] with K % ", km, " == 0",
+             nf4 ? c10::str(", got ", a.sizes()) : std::string());
   const long M = a.size(0), K = a.size(1);
-  SHAI_CHECK(w.is_cuda() && w.dim() == 2 && w.is_contiguous() && w.size(1) * 2 == K &&
-                 reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-             "mxfp4 gemm: w must be a contiguous, 16-byte aligned float4_e2m1fn_x2 [N, K / 2] matrix, got ", w.sizes(),
+  SHAI_CHECK(w.is_cuda() && (!nf4 || w.scalar_type() == at::kByte) && w.dim() == 2 && w.is_contiguous() &&
+                 w.size(1) * 2 == K && reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
+             f.name, " gemm: w must be a contiguous, 16-byte aligned ", f.w_dtype, " [N, K / 2] matrix, got ", w.sizes(),
              " for K = ", K);
   const long N = w.size(0);
-  SHAI_CHECK(w_scale.has_value(), "mxfp4 gemm: w_scale (the e8m0 group scales of quantize_mxfp4) is required");
+  SHAI_CHECK(w_scale.has_value(), f.name, " gemm: w_scale (", f.scale_what, ") is required");
   const Tensor& sc = *w_scale;
-  SHAI_CHECK(sc.is_cuda() && sc.get_device() == w.get_device() &&
-                 (sc.scalar_type() == at::ScalarType::Float8_e8m0fnu || sc.scalar_type() == at::kByte) &&
-                 sc.is_contiguous() && sc.dim() == 3 && sc.size(0) == (K + 127) / 128 && sc.size(1) == N &&
-                 sc.size(2) == 4 && reinterpret_cast<uintptr_t>(sc.data_ptr()) % 4 == 0,
-             "mxfp4 gemm: w_scale must be contiguous float8_e8m0fnu [ceil(K / 128), N, 4], got ", sc.sizes());
+  const bool sc_dtype = nf4 ? sc.scalar_type() == at::kFloat
+                            : sc.scalar_type() == at::ScalarType::Float8_e8m0fnu || sc.scalar_type() == at::kByte;
+  SHAI_CHECK(sc.is_cuda() && sc.get_device() == w.get_device() && sc_dtype && sc.is_contiguous() && sc.dim() == 3 &&
+                 sc.size(0) == (K + 127) / 128 && sc.size(1) == N && sc.size(2) == f.scales_per_step &&
+                 reinterpret_cast<uintptr_t>(sc.data_ptr()) % 4 == 0,
+             f.name, " gemm: w_scale must be contiguous ", f.scale_dtype, " [ceil(K / 128), N, ", f.scales_per_step,
+             "], got ", sc.sizes());
   check_bf16(c, "c");
-  SHAI_CHECK(N % 2 == 0 && (!glu || N % 4 == 0), "mxfp4 gemm: N must be even (glu: N % 4 == 0)");
+  SHAI_CHECK(N % 2 == 0 && (!glu || N % 4 == 0), f.name, " gemm: N must be even (glu: N % 4 == 0)");
   SHAI_CHECK(c.dim() == 2 && c.size(0) == M && c.size(1) == (glu ? N / 2 : N), "gemm output shape mismatch ", c.sizes());
   shai::GemmArgs g{};
   g.A = cptr(a);
   g.W = reinterpret_cast<const shai::bf16_t*>(w.data_ptr());
-  g.w_mx_scale = reinterpret_cast<const uint8_t*>(sc.data_ptr());
+  if (nf4) g.w_nf4_absmax = sc.data_ptr<float>();
+  else g.w_mx_scale = reinterpret_cast<const uint8_t*>(sc.data_ptr());
   g.C = mptr(c);
   g.M = (int)M;
   g.K = (int)K;
@@ -1008,13 +986,17 @@ void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optiona
   g.res_alpha = res_alpha;
   g.act = act;
   g.glu = glu;
+  if (rms_eps >= 0) {  // folded RMSNorm: rstd in fp32 inside the kernel ...
+    g.rms = 1;
+    g.rms_eps = (float)rms_eps;
+  }
   if (M > 64) {  // the tile kernel
     const int ft = (int)(force_cfg - kFp4TileCfg) / 32, fs = (int)(force_cfg - kFp4TileCfg) % 32;
-    SHAI_CHECK(force_cfg < 0 || (force_cfg >= kFp4TileCfg && ft < shai::gemm_fp4_num_tiles() && fs <= 16),
-               "mxfp4 gemm: bad force_cfg ", force_cfg, " for M = ", M,
-               " > 64: 1300 + 32 * tile + splits (tile 0..", shai::gemm_fp4_num_tiles() - 1, ", splits 0..16)");
+    SHAI_CHECK(force_cfg < 0 || (force_cfg >= kFp4TileCfg && ft < shai::kQ4Tiles && fs <= 16), f.name,
+               " gemm: bad force_cfg ", force_cfg, " for M = ", M, " > 64: 1300 + 32 * tile + splits (tile 0..",
+               shai::kQ4Tiles - 1, ", splits 0..16)");
     Tensor xn;
-    if (rms_eps >= 0) {  // folded RMSNorm above 64 rows: the explicit unweighted pass, as on the bf16 tile kernels
+    if (g.rms && !f.tile_folds_rms) {  // ... or the explicit unweighted pass first, as on the bf16 tile kernels
       SHAI_CHECK(K % 8 == 0 && K <= 8192, "folded RMSNorm: K must be a multiple of 8 and <= 8192");
       xn = at::empty({M, K}, a.options());
       shai::RowNormArgs r{};
@@ -1028,105 +1010,20 @@ void gemm_mxfp4(const Tensor& a, const Tensor& w, const Tensor& c, const optiona
       shai::launch_rmsnorm(r, stream());
       g.A = cptr(xn);
       g.lda = K;
+      g.rms = 0;
     }
-    SHAI_CHECK(shai::gemm_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 tile kernel");
-    if (force_cfg >= 0) launch_choice(g, a, Choice{kFp4TileCfg + 32 * ft, fs > 0 ? fs : shai::gemm_fp4_splits(g, ft)});
+    SHAI_CHECK(f.tile.supported(g), f.name, " gemm: problem not supported by the ", f.kernel, " tile kernel");
+    if (force_cfg >= 0) launch_choice(g, a, Choice{kFp4TileCfg + 32 * ft, fs > 0 ? fs : f.tile.splits(g, ft)});
     else run_fp4_tile(g, a);
     return;
   }
-  if (rms_eps >= 0) {
-    g.rms = 1;
-    g.rms_eps = (float)rms_eps;
-  }
-  SHAI_CHECK(shai::skinny_fp4_supported(g), "mxfp4 gemm: problem not supported by the fp4 skinny kernel");
+  SHAI_CHECK(f.skinny.supported(g), f.name, " gemm: problem not supported by the ", f.kernel, " skinny kernel");
   SHAI_CHECK(force_cfg < 0 || (force_cfg >= kSkinnyCfg && force_cfg <= kSkinnyCfg + 64) ||
                  (force_cfg > kSkinnyFixCfg && force_cfg <= kSkinnyFixCfg + 64),
-             "mxfp4 gemm: bad force_cfg ", force_cfg, " for M = ", M, " <= 64: 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
+             f.name, " gemm: bad force_cfg ", force_cfg, " for M = ", M, " <= 64: 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
   if (force_cfg > kSkinnyFixCfg) launch_choice(g, a, Choice{kSkinnyFixCfg, (int)(force_cfg - kSkinnyFixCfg)});
   else if (force_cfg > kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, (int)(force_cfg - kSkinnyCfg)});
-  else if (force_cfg == kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, shai::skinny_fp4_kgroups(g)});
-  else run_skinny(g, a);
-}
-
-// NF4 weights (ops.quantize_nf4): w uint8 [N, K / 2] (two codes per byte, even k in the low nibble), w_scale the fp32
-// block maxima tiled per 128-wide K step, [ceil(K / 128), N, 2].  Activations a [M, K] of M <= 64 rows on the skinny
-// kernel (gemv_nf4.hip), more rows on the tile kernel (gemm_nf4.hip; both apply a folded RMSNorm's rstd in fp32 in
-// their epilogue); ops.linear dequantises gated / LayerNorm-folded / batched calls.  force_cfg (tests / tools; < 0: tuned per
-// shape), M <= 64: 1000 = the heuristic K-group count with the separate fold, 1000 + kg = kg K groups folded by the
-// separate kernel (1001 = no split), 1100 + kg = kg K groups fixed up inside the launch (1 <= kg <= 64), as for MXFP4.
-// M > 64: 1300 + 32 * tile + splits (tile 0 = 128 x 128, 1 = 256 x 128; splits 1..16, 0 = the heuristic count).  A
-// number of the other row range is a "bad force_cfg" error.
-void gemm_nf4(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tensor>& bias,
-              const optional<Tensor>& residual, double alpha, double res_alpha, int64_t act, bool glu,
-              int64_t force_cfg, double rms_eps, const optional<Tensor>& w_scale) {
-  SHAI_CHECK(a.dim() == 2 && a.size(0) >= 1 && a.size(1) >= 64 && a.size(1) % 64 == 0,
-             "nf4 gemm: a must be a 2-D activation [M >= 1, K] with K % 64 == 0, got ", a.sizes());
-  const long M = a.size(0), K = a.size(1);
-  SHAI_CHECK(w.is_cuda() && w.scalar_type() == at::kByte && w.dim() == 2 && w.is_contiguous() && w.size(1) * 2 == K &&
-                 reinterpret_cast<uintptr_t>(w.data_ptr()) % 16 == 0,
-             "nf4 gemm: w must be a contiguous, 16-byte aligned uint8 [N, K / 2] matrix, got ", w.sizes(), " for K = ", K);
-  const long N = w.size(0);
-  SHAI_CHECK(w_scale.has_value(), "nf4 gemm: w_scale (the fp32 absmax of quantize_nf4) is required");
-  const Tensor& am = *w_scale;
-  SHAI_CHECK(am.is_cuda() && am.get_device() == w.get_device() && am.scalar_type() == at::kFloat &&
-                 am.is_contiguous() && am.dim() == 3 && am.size(0) == (K + 127) / 128 && am.size(1) == N &&
-                 am.size(2) == 2 && reinterpret_cast<uintptr_t>(am.data_ptr()) % 4 == 0,
-             "nf4 gemm: w_scale must be contiguous float32 [ceil(K / 128), N, 2], got ", am.sizes());
-  check_bf16(c, "c");
-  SHAI_CHECK(N % 2 == 0 && (!glu || N % 4 == 0), "nf4 gemm: N must be even (glu: N % 4 == 0)");
-  SHAI_CHECK(c.dim() == 2 && c.size(0) == M && c.size(1) == (glu ? N / 2 : N), "gemm output shape mismatch ", c.sizes());
-  shai::GemmArgs g{};
-  g.A = cptr(a);
-  g.W = reinterpret_cast<const shai::bf16_t*>(w.data_ptr());
-  g.w_nf4_absmax = am.data_ptr<float>();
-  g.C = mptr(c);
-  g.M = (int)M;
-  g.K = (int)K;
-  g.N = (int)N;
-  g.lda = a.stride(0);
-  g.ldw = K / 2;  // bytes
-  g.ldc = c.stride(0);
-  g.batch = 1;
-  if (bias) {
-    check_bf16(*bias, "bias");
-    SHAI_CHECK(bias->numel() == N, "bias size");
-    g.bias = cptr(*bias);
-  }
-  if (residual) {
-    check_bf16(*residual, "residual");
-    SHAI_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == c.size(1), "residual shape");
-    g.residual = cptr(*residual);
-    g.ldr = residual->stride(0);
-  }
-  g.alpha = alpha;
-  g.res_alpha = res_alpha;
-  g.act = act;
-  g.glu = glu;
-  if (M > 64) {  // the tile kernel
-    const int ft = (int)(force_cfg - kFp4TileCfg) / 32, fs = (int)(force_cfg - kFp4TileCfg) % 32;
-    SHAI_CHECK(force_cfg < 0 || (force_cfg >= kFp4TileCfg && ft < shai::gemm_nf4_num_tiles() && fs <= 16),
-               "nf4 gemm: bad force_cfg ", force_cfg, " for M = ", M,
-               " > 64: 1300 + 32 * tile + splits (tile 0..", shai::gemm_nf4_num_tiles() - 1, ", splits 0..16)");
-    if (rms_eps >= 0) {  // folded RMSNorm: rstd in fp32 inside the tile kernel, as the skinny kernel has it
-      g.rms = 1;
-      g.rms_eps = (float)rms_eps;
-    }
-    SHAI_CHECK(shai::gemm_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 tile kernel");
-    if (force_cfg >= 0) launch_choice(g, a, Choice{kFp4TileCfg + 32 * ft, fs > 0 ? fs : shai::gemm_nf4_splits(g, ft)});
-    else run_fp4_tile(g, a);
-    return;
-  }
-  if (rms_eps >= 0) {
-    g.rms = 1;
-    g.rms_eps = (float)rms_eps;
-  }
-  SHAI_CHECK(shai::skinny_nf4_supported(g), "nf4 gemm: problem not supported by the nf4 skinny kernel");
-  SHAI_CHECK(force_cfg < 0 || (force_cfg >= kSkinnyCfg && force_cfg <= kSkinnyCfg + 64) ||
-                 (force_cfg > kSkinnyFixCfg && force_cfg <= kSkinnyFixCfg + 64),
-             "nf4 gemm: bad force_cfg ", force_cfg, " for M = ", M, " <= 64: 1000 (+ kg) or 1100 + kg (1 <= kg <= 64)");
-  if (force_cfg > kSkinnyFixCfg) launch_choice(g, a, Choice{kSkinnyFixCfg, (int)(force_cfg - kSkinnyFixCfg)});
-  else if (force_cfg > kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, (int)(force_cfg - kSkinnyCfg)});
-  else if (force_cfg == kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, shai::skinny_nf4_kgroups(g)});
+  else if (force_cfg == kSkinnyCfg) launch_choice(g, a, Choice{kSkinnyCfg, f.skinny.kgroups(g)});
   else run_skinny(g, a);
 }
 
@@ -1141,16 +1038,11 @@ void gemm(const Tensor& a, const Tensor& w, const Tensor& c, const optional<Tens
   SHAI_CHECK(res_rows == 0 || (residual.has_value() && a.dim() == 2 && !w_scale.has_value() &&
                                w.scalar_type() != at::ScalarType::Float4_e2m1fn_x2 && w.scalar_type() != at::kByte),
              "residual_rows: 2D bf16-weight GEMMs with a residual");
-  if (w.scalar_type() == at::ScalarType::Float4_e2m1fn_x2) {
-    SHAI_CHECK(!bias2d && !gate && !ln_mr && !ln_s && !gn_part && !ln_stats && w_slice_rows == 0,
-               "mxfp4 gemm: bias / activation / GLU / residual / folded RMSNorm epilogues only");
-    gemm_mxfp4(a, w, c, bias, residual, alpha, res_alpha, act, glu, force_cfg, rms_eps, w_scale);
-    return;
-  }
-  if (w.scalar_type() == at::kByte) {
-    SHAI_CHECK(!bias2d && !gate && !ln_mr && !ln_s && !gn_part && !ln_stats && w_slice_rows == 0,
-               "nf4 gemm: bias / activation / GLU / residual / folded RMSNorm epilogues only");
-    gemm_nf4(a, w, c, bias, residual, alpha, res_alpha, act, glu, force_cfg, rms_eps, w_scale);
+  if (w.scalar_type() == at::ScalarType::Float4_e2m1fn_x2 || w.scalar_type() == at::kByte) {
+    const shai::Q4Format& f = w.scalar_type() == at::kByte ? shai::kNf4 : shai::kMxfp4;
+    SHAI_CHECK(!bias2d && !gate && !ln_mr && !ln_s && !gn_part && !ln_stats && w_slice_rows == 0, f.name,
+               " gemm: bias / activation / GLU / residual / folded RMSNorm epilogues only");
+    gemm_q4(f, a, w, c, bias, residual, alpha, res_alpha, act, glu, force_cfg, rms_eps, w_scale);
     return;
   }
   if (w_scale.has_value()) {  // fp8 (e4m3) weights + fp32 per-row scale: skinny (decode-shaped) kernel only

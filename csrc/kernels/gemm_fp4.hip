@@ -36,7 +36,7 @@
 // (A 256 x 256 tile would need 2 x 81 KB of LDS; wider N at BM = 128 doubles the converts per CU for the same MFMAs.)
 // Resource table and measurements: profiles/mxfp4_prefill.md.
 // (buffer descriptor, zero-fill sentinel, e8m0_scale and fp4x8_widen: skinny_common.h, shared with gemv_fp4.hip)
-#include "skinny_common.h"
+#include "q4_tile.h"
 
 namespace shai {
 
@@ -260,40 +260,11 @@ __global__ void __launch_bounds__(WM * WN * 64) gemm_fp4_kernel(const GemmArgs p
 // a.W: codes [N, K / 2] bytes at a row stride of a.ldw BYTES; a.w_mx_scale: [ceil(K / 128), N, 4] bytes.  Epilogues:
 // bias, activation, GLU (SILU / GELU / GELU_TANH), residual, alpha, row strides.  A folded RMSNorm (a.rms) is not
 // taken: the caller runs the unweighted row-norm pass first, as the bf16 tile kernels have it.
-bool gemm_fp4_supported(const GemmArgs& a) {
-  if (a.res_rows != 0) return false;  // no broadcast residual
-  return a.w_mx_scale != nullptr && a.w_scale == nullptr && !a.conv && a.batch <= 1 && a.w_slice_rows == 0 &&
-         a.M > 64 && a.K >= 32 && a.K % 32 == 0 && a.N >= 1 && a.N % 2 == 0 && (!a.glu || a.N % 4 == 0) &&
-         tile_act_supported(a) && !a.rms && a.bias2d == nullptr && a.gate == nullptr && a.in_scale == nullptr &&
-         a.A2 == nullptr && a.row_mr == nullptr && a.col_part == nullptr && a.row_part == nullptr &&
-         a.lda % 8 == 0 && a.ldw % 16 == 0 && a.ldw >= a.K / 2 && (long)a.N * a.ldw < 0x7fffffffL &&
-         (long)a.M * a.lda * 2 < 0x7fffffffL && (long)((a.K + G4_BK - 1) / G4_BK) * a.N * 4 < 0x7fffffffL;
+static bool gemm_fp4_supported(const GemmArgs& a) {
+  return a.w_mx_scale != nullptr && !a.rms && q4t_supported(a, 32, 4);
 }
 
-int gemm_fp4_num_tiles() { return 2; }
-
-static void g4_tile_dims(int tile, int* bm, int* bn) {
-  *bm = tile == 1 ? 256 : 128;
-  *bn = 128;
-}
-
-// heuristic tile: the 256-row tile once it alone gives every CU a workgroup
-int gemm_fp4_tile(const GemmArgs& a) { return (long)((a.M + 255) / 256) * ((a.N + 127) / 128) >= 256 ? 1 : 0; }
-
-// heuristic split count: up to one workgroup per CU (one fits), each split at least 4 K steps
-int gemm_fp4_splits(const GemmArgs& a, int tile) {
-  int bm, bn;
-  g4_tile_dims(tile, &bm, &bn);
-  const long tiles = (long)((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn);
-  const int ksteps = (a.K + G4_BK - 1) / G4_BK;
-  int s = 1;
-  while (s < 16 && tiles * s * 2 <= 256 && ksteps / (s * 2) >= 4) s *= 2;
-  return s;
-}
-
-int gemm_fp4_max_splits(const GemmArgs& a) { return max_kgroups((a.K + G4_BK - 1) / G4_BK); }
-
-size_t gemm_fp4_workspace_bytes(const GemmArgs& a, int splits) {
+static size_t gemm_fp4_workspace_bytes(const GemmArgs& a, int splits) {
   return splits > 1 ? (size_t)splits * a.M * a.N * sizeof(float) : 0;  // [split][M][N]
 }
 
@@ -313,13 +284,17 @@ static void launch_g4_tile(const GemmArgs& a, float* ws, int splits, int kg_step
   });
 }
 
-// tile: 0 = 128 x 128, 1 = 256 x 128; splits K groups (needs ws of gemm_fp4_workspace_bytes, else unsplit), folded by
-// launch_splitk_epilogue in split order
-void launch_gemm_fp4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s) {
-  const KSplit ks = split_ksteps((a.K + G4_BK - 1) / G4_BK, ws != nullptr ? splits : 1);
-  if (tile == 1) launch_g4_tile<256, 128, 2, 2, 2>(a, ws, ks.kg, ks.kg_steps, s);
-  else launch_g4_tile<128, 128, 2, 2, 3>(a, ws, ks.kg, ks.kg_steps, s);
-  if (ks.kg > 1) launch_splitk_epilogue(a, ws, ks.kg, s);
+static void launch_gemm_fp4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s) {
+  q4t_launch(a, ws, tile, splits, s, [&](int t, int kg, int kg_steps) {
+    if (t == 1) launch_g4_tile<256, 128, 2, 2, 2>(a, ws, kg, kg_steps, s);
+    else launch_g4_tile<128, 128, 2, 2, 3>(a, ws, kg, kg_steps, s);
+  });
+}
+
+const Q4TileOps& mxfp4_tile_ops() {
+  static const Q4TileOps ops = {gemm_fp4_supported,       q4t_tile,       q4t_splits, q4t_max_splits,
+                                gemm_fp4_workspace_bytes, launch_gemm_fp4};
+  return ops;
 }
 
 }  // namespace shai

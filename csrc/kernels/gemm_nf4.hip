@@ -46,7 +46,7 @@
 //   tile 0  128 x 128, 3 stages x (32 KB A + 8 KB codes + 1 KB absmax) = 123 KB, 64 accumulators per lane, IM = 4
 //   tile 1  256 x 128, 2 stages x (64 + 8 + 1 KB) = 146 KB, 128 accumulators per lane, IM = 8
 // Resource table and measurements: profiles/nf4_prefill.md.
-#include "skinny_common.h"
+#include "q4_tile.h"
 
 namespace shai {
 
@@ -323,37 +323,11 @@ __global__ void __launch_bounds__(256) gemm_nf4_kernel(const GemmArgs p, float* 
 // bias, activation, GLU (SILU / GELU / GELU_TANH), residual, alpha, row strides, folded RMSNorm (a.rms: rstd in fp32 in
 // front of the epilogue; an explicit row-norm pass would round the normalised activations to bf16, 1.3 ulp of error in
 // a GLU output where the skinny kernel's rule allows 1).
-bool gemm_nf4_supported(const GemmArgs& a) {
-  if (a.res_rows != 0) return false;  // no broadcast residual
-  return a.w_nf4_absmax != nullptr && a.w_scale == nullptr && a.w_mx_scale == nullptr && !a.conv && a.batch <= 1 &&
-         a.w_slice_rows == 0 && a.M > 64 && a.K >= 64 && a.K % 64 == 0 && a.N >= 1 && a.N % 2 == 0 &&
-         (!a.glu || a.N % 4 == 0) && tile_act_supported(a) && a.bias2d == nullptr && a.gate == nullptr &&
-         a.in_scale == nullptr && a.A2 == nullptr && a.row_mr == nullptr && a.col_part == nullptr &&
-         a.row_part == nullptr && a.lda % 8 == 0 && a.ldw % 16 == 0 && a.ldw >= a.K / 2 &&
-         (long)a.N * a.ldw < 0x7fffffffL && (long)a.M * a.lda * 2 < 0x7fffffffL &&
-         (long)((a.K + GN_BK - 1) / GN_BK) * a.N * 8 < 0x7fffffffL;
+static bool gemm_nf4_supported(const GemmArgs& a) {
+  return a.w_nf4_absmax != nullptr && a.w_mx_scale == nullptr && q4t_supported(a, 64, 8);
 }
 
-int gemm_nf4_num_tiles() { return 2; }
-
-static int gn_tile_rows(int tile) { return tile == 1 ? 256 : 128; }
-
-// heuristic tile: the 256-row tile once it alone gives every CU a workgroup
-int gemm_nf4_tile(const GemmArgs& a) { return (long)((a.M + 255) / 256) * ((a.N + GN_BN - 1) / GN_BN) >= 256 ? 1 : 0; }
-
-// heuristic split count: up to one workgroup per CU (one fits), each split at least 4 K steps
-int gemm_nf4_splits(const GemmArgs& a, int tile) {
-  const int bm = gn_tile_rows(tile);
-  const long tiles = (long)((a.M + bm - 1) / bm) * ((a.N + GN_BN - 1) / GN_BN);
-  const int ksteps = (a.K + GN_BK - 1) / GN_BK;
-  int s = 1;
-  while (s < 16 && tiles * s * 2 <= 256 && ksteps / (s * 2) >= 4) s *= 2;
-  return s;
-}
-
-int gemm_nf4_max_splits(const GemmArgs& a) { return max_kgroups((a.K + GN_BK - 1) / GN_BK); }
-
-size_t gemm_nf4_workspace_bytes(const GemmArgs& a, int splits) {
+static size_t gemm_nf4_workspace_bytes(const GemmArgs& a, int splits) {
   // [split][M][N], then [split][M] partial row sums of squares under a folded RMSNorm
   return splits > 1 ? ((size_t)splits * a.M * a.N + (a.rms ? (size_t)splits * a.M : 0)) * sizeof(float) : 0;
 }
@@ -375,13 +349,17 @@ static void launch_gn_tile(const GemmArgs& a, float* ws, int splits, int kg_step
   });
 }
 
-// tile: 0 = 128 x 128, 1 = 256 x 128; splits K groups (needs ws of gemm_nf4_workspace_bytes, else unsplit), folded by
-// launch_splitk_epilogue in split order
-void launch_gemm_nf4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s) {
-  const KSplit ks = split_ksteps((a.K + GN_BK - 1) / GN_BK, ws != nullptr ? splits : 1);
-  if (tile == 1) launch_gn_tile<256, 2>(a, ws, ks.kg, ks.kg_steps, s);
-  else launch_gn_tile<128, 3>(a, ws, ks.kg, ks.kg_steps, s);
-  if (ks.kg > 1) launch_splitk_epilogue(a, ws, ks.kg, s);
+static void launch_gemm_nf4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s) {
+  q4t_launch(a, ws, tile, splits, s, [&](int t, int kg, int kg_steps) {
+    if (t == 1) launch_gn_tile<256, 2>(a, ws, kg, kg_steps, s);
+    else launch_gn_tile<128, 3>(a, ws, kg, kg_steps, s);
+  });
+}
+
+const Q4TileOps& nf4_tile_ops() {
+  static const Q4TileOps ops = {gemm_nf4_supported,       q4t_tile,       q4t_splits, q4t_max_splits,
+                                gemm_nf4_workspace_bytes, launch_gemm_nf4};
+  return ops;
 }
 
 }  // namespace shai

@@ -43,6 +43,7 @@ namespace shai {
 
 struct WMxfp4 {
   static constexpr int BK = 128, SLICES = 8;  // K per step (4 scale groups), its k16 slices
+  static constexpr int K_MULT = 32, S_ROW = 4;  // K % 32 == 0 (a scale group); scale bytes per W row and step
   static constexpr bool FOLD = true, QUAD_STORES = true;
   static constexpr int W_BYTES = SR_BN * BK / 2;  // 8 KB of codes
   static constexpr int S_BYTES = 4 * 256;         // one 64-lane x 4-B DMA per wave (upper 32 lanes zero fill)
@@ -126,14 +127,6 @@ struct WMxfp4 {
   };
 };
 
-// ring depth: 4 stages (M <= 32) / 3 (M <= 64), two workgroups per CU either way
-template <int MB>
-struct Q4Geom {
-  static constexpr int STAGES = MB == 32 ? 4 : 3;
-  static constexpr size_t LDS = (size_t)STAGES * WMxfp4::stage_bytes(MB);
-  static constexpr int SLAB = SR_BN * MB + MB;  // floats of one (tile, K group) slab of the fixup
-};
-
 // MXFP4 codes + tiled scales -> bf16 [N, K] (prefill-shaped problems run the bf16 GEMMs on it): one thread per
 // scale group (16 B of codes -> 64 B of bf16)
 __global__ void __launch_bounds__(256) dequant_mxfp4_kernel(const uint8_t* __restrict__ wq,
@@ -162,57 +155,12 @@ void launch_dequant_mxfp4(const uint8_t* wq, const uint8_t* scales, bf16_t* out,
 
 // ---------------------------------------------------------------------------- host side
 // a.W: codes [N, K / 2] bytes at a row stride of a.ldw BYTES; a.w_mx_scale: [ceil(K / 128), N, 4] bytes
-bool skinny_fp4_supported(const GemmArgs& a) {
-  if (a.res_rows != 0) return false;  // no broadcast residual
-  return a.w_mx_scale != nullptr && a.w_scale == nullptr && !a.conv && a.batch <= 1 && a.w_slice_rows == 0 &&
-         a.M >= 1 && a.M <= 64 && a.K >= 32 && a.K % 32 == 0 && a.N >= 1 && a.N % 2 == 0 && (!a.glu || a.N % 4 == 0) &&
-         a.bias2d == nullptr && a.gate == nullptr && a.in_scale == nullptr && a.row_mr == nullptr &&
-         a.col_part == nullptr && a.row_part == nullptr && a.lda % 8 == 0 && a.ldw % 16 == 0 && a.ldw >= a.K / 2 &&
-         (long)a.N * a.ldw < 0x7fffffffL && (long)a.M * a.lda * 2 < 0x7fffffffL &&
-         (long)((a.K + WMxfp4::BK - 1) / WMxfp4::BK) * a.N * 4 < 0x7fffffffL;
-}
+// (K groups, workspace, launch: the q4_skinny_* templates of skinny_common.h, shared with gemv_nf4.hip)
+static bool skinny_fp4_supported(const GemmArgs& a) { return a.w_mx_scale != nullptr && q4_skinny_supported<WMxfp4>(a); }
 
-// K groups: about one workgroup per CU (two fit), each group at least 4 K steps
-int skinny_fp4_kgroups(const GemmArgs& a) {
-  const int tiles = (a.N + SR_BN - 1) / SR_BN, ksteps = (a.K + WMxfp4::BK - 1) / WMxfp4::BK;
-  int kg = 1;
-  while (tiles * kg < 256 && ksteps / (kg * 2) >= 4) kg *= 2;
-  return kg;
-}
-
-int skinny_fp4_max_kgroups(const GemmArgs& a) { return max_kgroups((a.K + WMxfp4::BK - 1) / WMxfp4::BK); }
-
-size_t skinny_fp4_workspace_bytes(const GemmArgs& a, int kg) {
-  if (kg <= 1) return 0;
-  const size_t fold = (size_t)kg * a.M * a.N + (size_t)kg * a.M;  // [kg][M][N] + row sums of squares
-  const int slab = a.M <= 32 ? Q4Geom<32>::SLAB : Q4Geom<64>::SLAB;
-  const size_t fix = (size_t)((a.N + SR_BN - 1) / SR_BN) * kg * (size_t)slab;  // [tile][kg] slabs
-  return (fold > fix ? fold : fix) * sizeof(float);
-}
-
-template <int MB>
-static void launch_fp4_mb(const GemmArgs& a, float* ws, KSplit ks, unsigned* cnt, hipStream_t s) {
-  const dim3 grid((a.N + SR_BN - 1) / SR_BN, ks.kg), block(256);
-  using G = Q4Geom<MB>;
-  dispatch_epilogue<kActsAll>(a, [&](auto glu, auto act, auto rms) {
-    skinny_rows_kernel<WMxfp4, MB, glu(), act(), rms(), G::STAGES><<<grid, block, G::LDS, s>>>(a, ws, ks.kg_steps, cnt);
-  });
-}
-
-// kg K groups (needs ws of skinny_fp4_workspace_bytes, else kg = 1); fixup: reduce the split-K partials inside the
-// launch when a ticket slice is available, else (and without fixup) the separate fold kernel
-void launch_skinny_fp4(const GemmArgs& a_in, float* ws, int kg, bool fixup, hipStream_t s) {
-  GemmArgs a = a_in;
-  a.w_nt = skinny_nt();
-  const int tiles = (a.N + SR_BN - 1) / SR_BN;
-  const KSplit ks = split_ksteps((a.K + WMxfp4::BK - 1) / WMxfp4::BK, ws != nullptr ? kg : 1);
-  unsigned* cnt = nullptr;
-  const int slab = a.M <= 32 ? Q4Geom<32>::SLAB : Q4Geom<64>::SLAB;
-  // (the slabs are addressed through one buffer descriptor: past 2 GiB the fold kernel takes the split)
-  if (ks.kg > 1 && fixup && (long)tiles * ks.kg * slab * 4 < 0x7fffffffL) cnt = skinny_ticket_slice(s, tiles);
-  if (a.M <= 32) launch_fp4_mb<32>(a, ws, ks, cnt, s);
-  else launch_fp4_mb<64>(a, ws, ks, cnt, s);
-  if (ks.kg > 1 && cnt == nullptr) launch_splitk_epilogue(a, ws, ks.kg, s);
+const Q4SkinnyOps& mxfp4_skinny_ops() {
+  static const Q4SkinnyOps ops = q4_skinny_ops<WMxfp4>(skinny_fp4_supported);
+  return ops;
 }
 
 }  // namespace shai

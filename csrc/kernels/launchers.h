@@ -244,45 +244,59 @@ int skinny2_max_kgroups(const GemmArgs& a);
 size_t skinny2_workspace_bytes(const GemmArgs& a, int kg);
 void launch_skinny2(const GemmArgs& a, float* ws, int kg, bool deep, hipStream_t s);
 void gemm2_cfg_info(int cfg, int* bm, int* bn);
-// MXFP4 skinny kernel (gemv_fp4.hip): 128-row W tiles x 128-wide K steps, M <= 64, GemmArgs::w_mx_scale set; split-K
-// over kg workgroups per tile (ws of skinny_fp4_workspace_bytes), folded by launch_splitk_epilogue or, fixup = true
-// and a ticket slice available, inside the launch
-bool skinny_fp4_supported(const GemmArgs& a);
-int skinny_fp4_kgroups(const GemmArgs& a);       // heuristic K-group count
-int skinny_fp4_max_kgroups(const GemmArgs& a);   // largest K-group count worth trying (autotuner)
-size_t skinny_fp4_workspace_bytes(const GemmArgs& a, int kg);
-void launch_skinny_fp4(const GemmArgs& a, float* ws, int kg, bool fixup, hipStream_t s);
-// MXFP4 tile GEMM (gemm_fp4.hip): M > 64, GemmArgs::w_mx_scale set, bf16 MFMA on codes widened in registers; bias /
-// activation / GLU / residual epilogues (no folded RMSNorm: the caller normalises the rows first).  tile 0 = 128 x 128,
-// 1 = 256 x 128; split-K over `splits` K groups (ws of gemm_fp4_workspace_bytes) folded by launch_splitk_epilogue
-bool gemm_fp4_supported(const GemmArgs& a);
-int gemm_fp4_num_tiles();
-int gemm_fp4_tile(const GemmArgs& a);               // heuristic tile config
-int gemm_fp4_splits(const GemmArgs& a, int tile);   // heuristic split count of that tile
-int gemm_fp4_max_splits(const GemmArgs& a);         // largest split count worth trying (autotuner)
-size_t gemm_fp4_workspace_bytes(const GemmArgs& a, int splits);
-void launch_gemm_fp4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s);
+// ---- 4-bit weight formats: MXFP4 (GemmArgs::w_mx_scale set; gemv_fp4.hip, gemm_fp4.hip) and NF4
+// (GemmArgs::w_nf4_absmax set; gemv_nf4.hip, gemm_nf4.hip).  Each format has a skinny kernel for M <= 64 and a tile
+// kernel above, described by one record; the host arithmetic both formats share is in skinny_common.h / q4_tile.h.
+// The skinny kernel: 128-row W tiles x 128-wide K steps; split-K over kg workgroups per tile (ws of workspace_bytes),
+// folded by launch_splitk_epilogue or, fixup = true and a ticket slice available, inside the launch
+struct Q4SkinnyOps {
+  bool (*supported)(const GemmArgs& a);
+  int (*kgroups)(const GemmArgs& a);       // heuristic K-group count
+  int (*max_kgroups)(const GemmArgs& a);   // largest K-group count worth trying (autotuner)
+  size_t (*workspace_bytes)(const GemmArgs& a, int kg);
+  void (*launch)(const GemmArgs& a, float* ws, int kg, bool fixup, hipStream_t s);
+};
+// The tile kernel: bf16 MFMA on codes widened in registers; bias / activation / GLU / residual epilogues.  tile 0 =
+// 128 x 128, 1 = 256 x 128 (kQ4Tiles); split-K over `splits` K groups (ws of workspace_bytes) folded by
+// launch_splitk_epilogue
+constexpr int kQ4Tiles = 2;
+struct Q4TileOps {
+  bool (*supported)(const GemmArgs& a);
+  int (*tile)(const GemmArgs& a);               // heuristic tile config
+  int (*splits)(const GemmArgs& a, int tile);   // heuristic split count of that tile
+  int (*max_splits)(const GemmArgs& a);         // largest split count worth trying (autotuner)
+  size_t (*workspace_bytes)(const GemmArgs& a, int splits);
+  void (*launch)(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s);
+};
+// (functions, not objects: a constant-initialised object of a .hip file is also emitted as device code, where the
+// host functions it points to do not exist)
+const Q4SkinnyOps& mxfp4_skinny_ops();  // gemv_fp4.hip
+const Q4SkinnyOps& nf4_skinny_ops();    // gemv_nf4.hip
+const Q4TileOps& mxfp4_tile_ops();      // gemm_fp4.hip
+const Q4TileOps& nf4_tile_ops();        // gemm_nf4.hip
+struct Q4Format {
+  const char* name;        // "mxfp4" / "nf4": the "<name> gemm:" of messages, the "|<name>w" of tuning keys
+  const char* kernel;      // "fp4" / "nf4": "the <kernel> tile kernel" of messages
+  int k_multiple;          // K % k_multiple == 0: the scale group (32) / the block (64)
+  int scale_size;          // bytes of a scale element: e8m0 byte / fp32 absmax
+  int scales_per_step;     // scale elements per W row and 128-wide K step: the scale tensor is [ceil(K / 128), N, this]
+  const char* w_dtype;     // names of messages: the code tensor's dtype, the scale tensor's dtype, what the scales are
+  const char* scale_dtype;
+  const char* scale_what;
+  bool tile_folds_rms;     // the tile kernel applies a folded RMSNorm itself (else: an explicit row-norm pass first)
+  const Q4SkinnyOps& skinny;
+  const Q4TileOps& tile;
+};
+inline const Q4Format kMxfp4 = {"mxfp4", "fp4", 32, 1, 4, "float4_e2m1fn_x2", "float8_e8m0fnu",
+                                "the e8m0 group scales of quantize_mxfp4", false, mxfp4_skinny_ops(), mxfp4_tile_ops()};
+inline const Q4Format kNf4 = {"nf4", "nf4", 64, 4, 2, "uint8", "float32",
+                              "the fp32 absmax of quantize_nf4", true, nf4_skinny_ops(), nf4_tile_ops()};
+// the 4-bit format of a problem's weights, nullptr for bf16 / fp8 weights
+inline const Q4Format* q4_format(const GemmArgs& a) {
+  return a.w_nf4_absmax != nullptr ? &kNf4 : a.w_mx_scale != nullptr ? &kMxfp4 : nullptr;
+}
 // MXFP4 codes [N, K / 2] + tiled scales [ceil(K / 128), N, 4] -> bf16 [N, K] (K % 32 == 0)
 void launch_dequant_mxfp4(const uint8_t* wq, const uint8_t* scales, bf16_t* out, long N, int K, hipStream_t s);
-// NF4 skinny kernel (gemv_nf4.hip): 128-row W tiles x 128-wide K steps (two blocks of 64), M <= 64,
-// GemmArgs::w_nf4_absmax set; split-K over kg workgroups per tile (ws of skinny_nf4_workspace_bytes), folded by
-// launch_splitk_epilogue or, fixup = true and a ticket slice available, inside the launch
-bool skinny_nf4_supported(const GemmArgs& a);
-int skinny_nf4_kgroups(const GemmArgs& a);       // heuristic K-group count
-int skinny_nf4_max_kgroups(const GemmArgs& a);   // largest K-group count worth trying (autotuner)
-size_t skinny_nf4_workspace_bytes(const GemmArgs& a, int kg);
-void launch_skinny_nf4(const GemmArgs& a, float* ws, int kg, bool fixup, hipStream_t s);
-// NF4 tile GEMM (gemm_nf4.hip): M > 64, GemmArgs::w_nf4_absmax set, bf16 MFMA on codes widened in registers (waves
-// striped over N); bias / activation / GLU / residual / folded RMSNorm epilogues.
-// tile 0 = 128 x 128, 1 = 256 x 128; split-K over `splits` K groups (ws of gemm_nf4_workspace_bytes) folded by
-// launch_splitk_epilogue
-bool gemm_nf4_supported(const GemmArgs& a);
-int gemm_nf4_num_tiles();
-int gemm_nf4_tile(const GemmArgs& a);               // heuristic tile config
-int gemm_nf4_splits(const GemmArgs& a, int tile);   // heuristic split count of that tile
-int gemm_nf4_max_splits(const GemmArgs& a);         // largest split count worth trying (autotuner)
-size_t gemm_nf4_workspace_bytes(const GemmArgs& a, int splits);
-void launch_gemm_nf4(const GemmArgs& a, float* ws, int tile, int splits, hipStream_t s);
 // NF4 codes [N, K / 2] + tiled absmax [ceil(K / 128), N, 2] -> bf16 [N, K] (K % 64 == 0)
 void launch_dequant_nf4(const uint8_t* wq, const float* absmax, bf16_t* out, long N, int K, hipStream_t s);
 

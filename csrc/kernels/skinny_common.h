@@ -8,7 +8,8 @@
 //   * skinny_rows_kernel<Fmt, MB, GLU, ACT, RMS, STAGES>: the wide body.  Fmt (WBf16 in gemv2.hip, WMxfp4 in
 //     gemv_fp4.hip) says how a K step's bytes reach LDS and become bf16 fragments; ring, waits, folded RMSNorm,
 //     epilogues and the split-K fixup are written once here;
-//   * host helpers: the SHAI_SKINNY_NT switch, K-group arithmetic, the GLU x activation x RMS dispatch.
+//   * host helpers: the SHAI_SKINNY_NT switch, K-group arithmetic, the GLU x activation x RMS dispatch, and the host
+//     side of the 4-bit skinny kernels (gemv_fp4.hip, gemv_nf4.hip) templated on their format policy.
 #pragma once
 #include "common.h"
 #include "launchers.h"
@@ -442,6 +443,90 @@ inline void dispatch_epilogue(const GemmArgs& a, F&& f) {
   };
   if (a.glu) dispatch_act<GLU_ACTS, GLU_DFLT>(a.act, [&](auto act) { with_rms(std::true_type{}, act); });
   else dispatch_act<ACTS, ACT_NONE>(a.act, [&](auto act) { with_rms(std::false_type{}, act); });
+}
+
+// ---------------------------------------------------------------------------- host side of the 4-bit weight formats
+// What every kernel over 4-bit weights asks of a problem beside its own terms (skinny and tile kernels, both formats).
+// a.W: codes [N, K / 2] bytes at a row stride of a.ldw BYTES; scales tiled [ceil(K / 128), N, sb bytes].  kmult: the
+// format's K multiple (scale group 32 / block 64); sb: bytes of scales per W row and 128-wide K step
+inline bool q4_weights_supported(const GemmArgs& a, int kmult, int sb) {
+  if (a.res_rows != 0) return false;  // no broadcast residual
+  return a.w_scale == nullptr && !a.conv && a.batch <= 1 && a.w_slice_rows == 0 && a.K >= kmult && a.K % kmult == 0 &&
+         a.N >= 1 && a.N % 2 == 0 && (!a.glu || a.N % 4 == 0) && a.bias2d == nullptr && a.gate == nullptr &&
+         a.in_scale == nullptr && a.row_mr == nullptr && a.col_part == nullptr && a.row_part == nullptr &&
+         a.lda % 8 == 0 && a.ldw % 16 == 0 && a.ldw >= a.K / 2 && (long)a.N * a.ldw < 0x7fffffffL &&
+         (long)a.M * a.lda * 2 < 0x7fffffffL && (long)((a.K + 127) / 128) * a.N * sb < 0x7fffffffL;
+}
+
+// The skinny kernels of the 4-bit formats, Fmt = WMxfp4 (gemv_fp4.hip) / WNf4 (gemv_nf4.hip).
+// Ring depth: two workgroups per CU, each with the deepest ring that fits its 80 KB (gemv_nf4.hip derives it; the
+// stage of both formats is 8 KB of codes + 1 KB of scales + 8 / 16 KB of X): 4 stages (M <= 32) / 3 (M <= 64)
+template <class Fmt, int MB>
+struct Q4SkinnyGeom {
+  static constexpr int STAGES = (80 * 1024) / Fmt::stage_bytes(MB);
+  static_assert(STAGES >= 3, "the ring needs two steps in flight beside the one consumed");
+  static constexpr size_t LDS = (size_t)STAGES * Fmt::stage_bytes(MB);
+  static constexpr int SLAB = SR_BN * MB + MB;  // floats of one (tile, K group) slab of the fixup
+};
+
+template <class Fmt>
+inline bool q4_skinny_supported(const GemmArgs& a) {
+  return a.M >= 1 && a.M <= 64 && q4_weights_supported(a, Fmt::K_MULT, Fmt::S_ROW);
+}
+
+// K groups: about one workgroup per CU (two fit), each group at least 4 K steps
+template <class Fmt>
+inline int q4_skinny_kgroups(const GemmArgs& a) {
+  const int tiles = (a.N + SR_BN - 1) / SR_BN, ksteps = (a.K + Fmt::BK - 1) / Fmt::BK;
+  int kg = 1;
+  while (tiles * kg < 256 && ksteps / (kg * 2) >= 4) kg *= 2;
+  return kg;
+}
+
+template <class Fmt>
+inline int q4_skinny_max_kgroups(const GemmArgs& a) { return max_kgroups((a.K + Fmt::BK - 1) / Fmt::BK); }
+
+template <class Fmt>
+inline size_t q4_skinny_workspace_bytes(const GemmArgs& a, int kg) {
+  if (kg <= 1) return 0;
+  const size_t fold = (size_t)kg * a.M * a.N + (size_t)kg * a.M;  // [kg][M][N] + row sums of squares
+  const int slab = a.M <= 32 ? Q4SkinnyGeom<Fmt, 32>::SLAB : Q4SkinnyGeom<Fmt, 64>::SLAB;
+  const size_t fix = (size_t)((a.N + SR_BN - 1) / SR_BN) * kg * (size_t)slab;  // [tile][kg] slabs
+  return (fold > fix ? fold : fix) * sizeof(float);
+}
+
+template <class Fmt, int MB>
+inline void launch_q4_skinny_mb(const GemmArgs& a, float* ws, KSplit ks, unsigned* cnt, hipStream_t s) {
+  const dim3 grid((a.N + SR_BN - 1) / SR_BN, ks.kg), block(256);
+  using G = Q4SkinnyGeom<Fmt, MB>;
+  dispatch_epilogue<kActsAll>(a, [&](auto glu, auto act, auto rms) {
+    skinny_rows_kernel<Fmt, MB, glu(), act(), rms(), G::STAGES><<<grid, block, G::LDS, s>>>(a, ws, ks.kg_steps, cnt);
+  });
+}
+
+// kg K groups (needs ws of q4_skinny_workspace_bytes, else kg = 1); fixup: reduce the split-K partials inside the
+// launch when a ticket slice is available, else (and without fixup) the separate fold kernel
+template <class Fmt>
+inline void launch_q4_skinny(const GemmArgs& a_in, float* ws, int kg, bool fixup, hipStream_t s) {
+  static_assert(Q4SkinnyGeom<Fmt, 32>::STAGES == 4 && Q4SkinnyGeom<Fmt, 64>::STAGES == 3, "ring depths of the header");
+  GemmArgs a = a_in;
+  a.w_nt = skinny_nt();
+  const int tiles = (a.N + SR_BN - 1) / SR_BN;
+  const KSplit ks = split_ksteps((a.K + Fmt::BK - 1) / Fmt::BK, ws != nullptr ? kg : 1);
+  unsigned* cnt = nullptr;
+  const int slab = a.M <= 32 ? Q4SkinnyGeom<Fmt, 32>::SLAB : Q4SkinnyGeom<Fmt, 64>::SLAB;
+  // (the slabs are addressed through one buffer descriptor: past 2 GiB the fold kernel takes the split)
+  if (ks.kg > 1 && fixup && (long)tiles * ks.kg * slab * 4 < 0x7fffffffL) cnt = skinny_ticket_slice(s, tiles);
+  if (a.M <= 32) launch_q4_skinny_mb<Fmt, 32>(a, ws, ks, cnt, s);
+  else launch_q4_skinny_mb<Fmt, 64>(a, ws, ks, cnt, s);
+  if (ks.kg > 1 && cnt == nullptr) launch_splitk_epilogue(a, ws, ks.kg, s);
+}
+
+// the format's record of launchers.h
+template <class Fmt>
+inline Q4SkinnyOps q4_skinny_ops(bool (*supported)(const GemmArgs&)) {
+  return {supported, q4_skinny_kgroups<Fmt>, q4_skinny_max_kgroups<Fmt>, q4_skinny_workspace_bytes<Fmt>,
+          launch_q4_skinny<Fmt>};
 }
 
 }  // namespace shai

@@ -35,13 +35,13 @@ std::vector<std::string> broadcast_refusals() {
   shai::GemmArgs f4 = g;  // MXFP4 weights: ldw in bytes
   f4.w_mx_scale = reinterpret_cast<const uint8_t*>(buf);
   f4.ldw = 96;
-  both("fp4", f4, 256, [](const shai::GemmArgs& a) { return shai::gemm_fp4_supported(a); });
+  both("fp4", f4, 256, [](const shai::GemmArgs& a) { return shai::kMxfp4.tile.supported(a); });
   shai::GemmArgs sk = g;  // decode-shaped
   sk.M = 64;
   both("skinny", sk, 32, [](const shai::GemmArgs& a) { return shai::skinny_supported(a); });
   both("skinny2", sk, 32, [](const shai::GemmArgs& a) { return shai::skinny2_supported(a); });
   f4.M = 64;
-  both("skinny_fp4", f4, 32, [](const shai::GemmArgs& a) { return shai::skinny_fp4_supported(a); });
+  both("skinny_fp4", f4, 32, [](const shai::GemmArgs& a) { return shai::kMxfp4.skinny.supported(a); });
   shai::GemmArgs h = g;  // 3x3 conv, 2 images of 64 x 64 x 64 -> 320
   h.conv = 1, h.Nimg = 2, h.H = h.Wd = h.OH = h.OW = 64, h.Cin = h.Cin1 = 64, h.KH = h.KW = 3, h.stride = h.pad = 1;
   h.M = 2 * 64 * 64, h.K = 9 * 64, h.lda = h.ldw = h.K;
@@ -71,6 +71,33 @@ std::vector<std::string> broadcast_refusals() {
   return out;
 }
 
+// Tests: the host decisions of the 4-bit weight paths (fmt "mxfp4" / "nf4") for a contiguous [M, K] x [N, K] problem,
+// GLU with SILU, folded RMSNorm on request.  Skinny kernel: supported, heuristic K groups, max K groups, workspace
+// bytes at kg = 4; tile kernel: supported, heuristic tile, its heuristic splits, max splits, workspace bytes at
+// splits = 4.  Host arithmetic only: the pointers are aligned placeholders, nothing is launched.
+std::vector<int64_t> q4_host_decisions(std::string fmt, int64_t M, int64_t N, int64_t K, bool glu, bool rms) {
+  alignas(16) static char buf[64];
+  TORCH_CHECK(fmt == shai::kNf4.name || fmt == shai::kMxfp4.name, "q4_host_decisions: fmt must be mxfp4 or nf4");
+  const bool nf4 = fmt == shai::kNf4.name;
+  shai::GemmArgs g{};
+  g.A = g.W = reinterpret_cast<const shai::bf16_t*>(buf);
+  g.C = reinterpret_cast<shai::bf16_t*>(buf);
+  if (nf4) g.w_nf4_absmax = reinterpret_cast<const float*>(buf);
+  else g.w_mx_scale = reinterpret_cast<const uint8_t*>(buf);
+  g.M = (int)M, g.N = (int)N, g.K = (int)K, g.lda = K, g.ldw = K / 2, g.ldc = glu ? N / 2 : N, g.batch = 1;
+  g.alpha = g.res_alpha = 1.f, g.rows_per_bias2d = g.rows_per_gate = 1;
+  g.glu = glu, g.act = glu ? 1 : 0;  // ACT_SILU
+  g.rms = rms, g.rms_eps = 1e-5f;
+  const shai::Q4Format& f = *shai::q4_format(g);
+  const int tile = f.tile.tile(g);
+  return {f.skinny.supported(g), f.skinny.kgroups(g), f.skinny.max_kgroups(g), (int64_t)f.skinny.workspace_bytes(g, 4),
+          f.tile.supported(g), tile, f.tile.splits(g, tile), f.tile.max_splits(g),
+          (int64_t)f.tile.workspace_bytes(g, 4)};
+}
+
 }  // namespace
 
-TORCH_LIBRARY_FRAGMENT(shai, m) { m.def("broadcast_refusals() -> str[]", &broadcast_refusals); }
+TORCH_LIBRARY_FRAGMENT(shai, m) {
+  m.def("broadcast_refusals() -> str[]", &broadcast_refusals);
+  m.def("q4_host_decisions(str fmt, int M, int N, int K, bool glu, bool rms) -> int[]", &q4_host_decisions);
+}
