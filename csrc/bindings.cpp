@@ -2274,6 +2274,94 @@ void quant_rows_fp8(const Tensor& x, const Tensor& out, const Tensor& scale, dou
                               (float)rms_eps, stream());
 }
 
+// ---- sparse mixture-of-experts MLP (moe.hip).  Shapes are checked here; the support limits raise from the Python op.
+const uint16_t* bf16_ptr(const Tensor& t) { return reinterpret_cast<const uint16_t*>(t.data_ptr()); }
+
+void moe_route(const Tensor& x, const Tensor& wg, const Tensor& ids, const Tensor& weights, const Tensor& rstd,
+               double rms_eps) {
+  check_rows(x, "x");
+  check_f32(wg, "wg");
+  check_i32(ids, "ids");
+  check_f32(weights, "weights");
+  check_f32(rstd, "rstd");
+  SHAI_CHECK(x.dim() == 2 && wg.dim() == 2 && wg.size(1) == x.size(1) && ids.dim() == 2, "moe_route: x [M, H], wg [E, H]");
+  const int M = x.size(0), H = x.size(1), E = wg.size(0), k = ids.size(1);
+  SHAI_CHECK(shai::moe_supported(M, H, 64, E, k, 32), "moe_route: unsupported M / H / E / k");
+  SHAI_CHECK(ids.size(0) == M && weights.sizes() == ids.sizes() && rstd.numel() == M, "moe_route: output shapes");
+  shai::launch_moe_route(bf16_ptr(x), x.stride(0), wg.data_ptr<float>(), ids.data_ptr<int>(),
+                         weights.data_ptr<float>(), rstd.data_ptr<float>(), M, H, E, k, (float)rms_eps, rms_eps >= 0,
+                         stream());
+}
+
+void moe_glu(const Tensor& x, const Tensor& w13, const Tensor& ids, const optional<Tensor>& rstd, const Tensor& plan,
+             const Tensor& h, int64_t tm) {
+  check_rows(x, "x");
+  check_bf16(w13, "w13");
+  check_bf16(h, "h");
+  check_i32(ids, "ids");
+  check_i32(plan, "plan");
+  SHAI_CHECK(x.dim() == 2 && w13.dim() == 3 && w13.is_contiguous() && ids.dim() == 2 && h.dim() == 2 &&
+                 h.is_contiguous() && w13.size(2) == x.size(1) && w13.size(1) % 2 == 0,
+             "moe_glu: x [M, H], w13 [E, 2 I, H], ids [M, k], h [s_cap, I]");
+  const int M = x.size(0), H = x.size(1), E = w13.size(0), I = w13.size(1) / 2, k = ids.size(1);
+  SHAI_CHECK(shai::moe_supported(M, H, I, E, k, (int)tm), "moe_glu: unsupported M / H / I / E / k / tile rows");
+  int s_cap, words;
+  shai::moe_plan_dims(M, k, E, (int)tm, &s_cap, &words);
+  SHAI_CHECK(ids.size(0) == M && plan.numel() >= words && h.size(0) == s_cap && h.size(1) == I,
+             "moe_glu: ids / plan / h do not fit the problem");
+  const float* rs = nullptr;
+  if (rstd.has_value()) {
+    check_f32(*rstd, "rstd");
+    SHAI_CHECK(rstd->numel() == M, "moe_glu: rstd must hold one value per row");
+    rs = rstd->data_ptr<float>();
+  }
+  shai::launch_moe_glu(bf16_ptr(x), x.stride(0), bf16_ptr(w13), ids.data_ptr<int>(), rs, plan.data_ptr<int>(),
+                       reinterpret_cast<uint16_t*>(h.data_ptr()), M, H, I, E, k, (int)tm, stream());
+}
+
+void moe_down(const Tensor& h, const Tensor& w2, const Tensor& plan, const Tensor& weights, const Tensor& yslot,
+              const optional<Tensor>& residual, const Tensor& y, int64_t tm, int64_t splits) {
+  check_bf16(h, "h");
+  check_bf16(w2, "w2");
+  check_bf16(y, "y");
+  check_i32(plan, "plan");
+  check_f32(weights, "weights");
+  SHAI_CHECK(h.dim() == 2 && h.is_contiguous() && w2.dim() == 3 && w2.is_contiguous() && weights.dim() == 2 &&
+                 y.dim() == 2 && y.is_contiguous() && w2.size(2) == h.size(1) && y.size(1) == w2.size(1) &&
+                 weights.size(0) == y.size(0),
+             "moe_down: h [s_cap, I], w2 [E, H, I], weights [M, k], y [M, H]");
+  const int M = y.size(0), H = y.size(1), E = w2.size(0), I = w2.size(2), k = weights.size(1);
+  SHAI_CHECK(shai::moe_supported(M, H, I, E, k, (int)tm) && splits >= 1 && splits <= 16,
+             "moe_down: unsupported M / H / I / E / k / tile rows / splits");
+  int s_cap, words;
+  shai::moe_plan_dims(M, k, E, (int)tm, &s_cap, &words);
+  SHAI_CHECK(plan.numel() >= words && h.size(0) == s_cap, "moe_down: plan / h do not fit the problem");
+  SHAI_CHECK(yslot.is_cuda() && yslot.is_contiguous() &&
+                 (splits > 1 ? yslot.scalar_type() == at::kFloat && yslot.numel() >= splits * (int64_t)s_cap * H
+                             : yslot.scalar_type() == at::kBFloat16 && yslot.numel() >= (int64_t)s_cap * H),
+             "moe_down: yslot must be [s_cap, H] bf16, or [splits, s_cap, H] fp32 with splits > 1");
+  const uint16_t* res = nullptr;
+  long ldr = 0;
+  if (residual.has_value()) {
+    check_rows(*residual, "residual");
+    SHAI_CHECK(residual->dim() == 2 && residual->size(0) == M && residual->size(1) == H, "moe_down: residual [M, H]");
+    res = bf16_ptr(*residual);
+    ldr = residual->stride(0);
+  }
+  shai::launch_moe_down(bf16_ptr(h), bf16_ptr(w2), plan.data_ptr<int>(), weights.data_ptr<float>(), yslot.data_ptr(),
+                        res, ldr, reinterpret_cast<uint16_t*>(y.data_ptr()), M, H, I, E, k, (int)tm, (int)splits,
+                        stream());
+}
+
+// [tile rows, s_cap, plan words, down splits] of a problem; tile_rows / splits <= 0: the host's choice from M
+std::vector<int64_t> moe_dims(int64_t M, int64_t I, int64_t E, int64_t k, int64_t tile_rows, int64_t splits) {
+  const int tm = tile_rows > 0 ? (int)tile_rows : shai::moe_tile_rows((int)M);
+  SHAI_CHECK(tm == 32 || tm == 128, "moe: tile rows must be 32 or 128");
+  int s_cap, words;
+  shai::moe_plan_dims((int)M, (int)k, (int)E, tm, &s_cap, &words);
+  return {tm, s_cap, words, splits > 0 ? splits : shai::moe_down_splits((int)M, (int)I)};
+}
+
 TORCH_LIBRARY(shai, m) {
   m.def("from_ptr(int ptr, int[] size, ScalarType dtype, int device) -> Tensor", &from_ptr);
   m.def("gemm_f8(Tensor a8, Tensor w8, Tensor a_scale, Tensor w_scale, Tensor(a!) c, Tensor? bias, Tensor? residual, float res_alpha, int act, bool glu, int cfg=-1) -> ()");
@@ -2324,6 +2412,11 @@ TORCH_LIBRARY(shai, m) {
         "int num_splits, float scale, Tensor? qkv_ws=None, int qkv_kg=0, int qkv_k=0, float qkv_eps=-1.0, float k_scale=1.0, float v_scale=1.0) -> ()");
   m.def("gemm_partials(Tensor a, Tensor w, float rms_eps) -> Tensor");
   m.def("gemm_lnout(Tensor a, Tensor w, Tensor(a!) c, Tensor(b!) c2, Tensor? bias, Tensor residual, float res_alpha, Tensor? gamma, Tensor? beta, float eps, int res_rows=0) -> bool");
+  m.def("moe_route(Tensor x, Tensor wg, Tensor(a!) ids, Tensor(b!) weights, Tensor(c!) rstd, float rms_eps) -> ()");
+  m.def("moe_glu(Tensor x, Tensor w13, Tensor ids, Tensor? rstd, Tensor(a!) plan, Tensor(b!) h, int tile_rows) -> ()");
+  m.def("moe_down(Tensor h, Tensor w2, Tensor plan, Tensor weights, Tensor(a!) yslot, Tensor? residual, Tensor(b!) y, "
+        "int tile_rows, int splits) -> ()");
+  m.def("moe_dims(int M, int I, int E, int k, int tile_rows, int splits) -> int[]", &moe_dims);
   m.def("gemm_tuning() -> str[]", &gemm_tuning);
   m.def("gemm_tuning_export() -> str[]", &gemm_tuning_export);
   m.def("gemm_tuning_import(str[] entries) -> int", &gemm_tuning_import);
@@ -2374,4 +2467,7 @@ TORCH_LIBRARY_IMPL(shai, CUDA, m) {
   m.impl("token_feedback", &token_feedback);
   m.impl("decode_attn_rope", &decode_attn_rope);
   m.impl("gemm_partials", &gemm_partials);
+  m.impl("moe_route", &moe_route);
+  m.impl("moe_glu", &moe_glu);
+  m.impl("moe_down", &moe_down);
 }

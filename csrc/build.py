@@ -40,7 +40,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 KERNEL_SRCS = ["kernels/norm.hip", "kernels/gemm.hip", "kernels/gemm_lds.hip", "kernels/gemm_8ph.hip", "kernels/gemm_w4.hip", "kernels/gemm_ws.hip", "kernels/conv_halo.hip", "kernels/attention.hip", "kernels/attention2.hip", "kernels/attention3.hip", "kernels/elementwise.hip", "kernels/dit.hip",
                "kernels/sampling.hip", "kernels/gemv.hip", "kernels/gemv2.hip", "kernels/gemv_fp4.hip", "kernels/gemv_nf4.hip",
                "kernels/gemm_f8.hip", "kernels/attention_kv8.hip", "kernels/gemm_fp4.hip",
-               "kernels/attention_spec.hip", "kernels/gemm_nf4.hip"]
+               "kernels/attention_spec.hip", "kernels/gemm_nf4.hip", "kernels/moe.hip"]
 # kernels that must not spill, as source -> part of the kernel's mangled name: the source is compiled with the
 # resource-usage remarks on, and build() fails when one of the named kernels reports scratch (the fp8-cache
 # instantiations of the hand-scheduled split decode kernel sit near their register budget).  The kernels are picked
@@ -59,7 +59,10 @@ NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8",
               # the NF4 skinny instantiations hold eight gathered fp32 table values beside the accumulators
               "kernels/gemv_nf4.hip": "skinny_rows_kernelINS_4WNf4",
               # the NF4 tile GEMM: up to 128 accumulators, two A fragment sets and the gathered table values
-              "kernels/gemm_nf4.hip": "gemm_nf4_kernel"}
+              "kernels/gemm_nf4.hip": "gemm_nf4_kernel",
+              # the mixture-of-experts kernels: the router keeps 4 rows x 16 experts of partial dot products per lane,
+              # the grouping its 16 per-expert counters in registers, the grouped GEMM up to 64 accumulators
+              "kernels/moe.hip": ("moe_route_kernel", "moe_align_kernel", "moe_gemm_kernel", "moe_combine_kernel")}
 NO_SCRATCH_NAMES = [p for v in NO_SCRATCH.values() for p in ((v,) if isinstance(v, str) else v)]
 # per-source extra hipcc flags: gemm_w4's epilogue (256 accumulators x an activation) is larger than LLVM's
 # default pragma-unroll budget; partially unrolled it would index the accumulators at run time (scratch)
@@ -73,6 +76,7 @@ EXTRA_KFLAGS = {"kernels/attention3.hip": "-mllvm -amdgpu-mfma-vgpr-form -fno-sl
                 # products per step come out as 64 v_mul_f32 either way of counting (profiles/nf4_decode.md)
                 "kernels/gemv_nf4.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops",
                 "kernels/gemm_nf4.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops",
+                "kernels/moe.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops",
                 "kernels/gemm_ws.hip": "-mllvm -pragma-unroll-threshold=100000 -fno-slp-vectorize",
                 "kernels/conv_halo.hip": "-mllvm -pragma-unroll-threshold=100000 -fno-slp-vectorize"}
 # test_probes.cpp: test-only operators (host probes of the *_supported checks)

@@ -478,4 +478,22 @@ void launch_penalty_state_init(int* state_row, int V, const int* tokens, int n_t
 // value, ascending index).  row_n (or null): per-row count <= N, negative = skip the row.
 void launch_token_logprobs(const void* logits, bool bf16, long ld, int B, int V, const int* toks, const int* row_n,
                            int N, float* vals, int* ids, hipStream_t s);
+// ---- sparse mixture-of-experts MLP (moe.hip).  Supported: 2 <= E <= 16, k in {1, 2}, H % 64 == 0, I % 64 == 0, row
+// tile tm in {32, 128}.  Slot s = m k + j; the plan (int32 words, moe_plan_dims) holds the tile count, each tile's
+// expert, the slots sorted by expert (padded per expert to tm with -1) and pos[slot].
+bool moe_supported(int M, int H, int I, int E, int k, int tm);
+int moe_tile_rows(int M);           // the row-tile height the host picks from M
+int moe_down_splits(int M, int I);  // the K split count of the down GEMM the host picks from M
+void moe_plan_dims(int M, int k, int E, int tm, int* s_cap, int* plan_words);
+// ids [M, k], wts [M, k], rstd [M] (1 without rms) from x [M, H] (row stride ldx) and the fp32 router weight [E, H]
+void launch_moe_route(const bf16_t* x, long ldx, const float* wg, int* ids, float* wts, float* rstd, int M, int H,
+                      int E, int k, float eps, bool rms, hipStream_t s);
+// groups the slots by expert into plan, then h [s_cap, I] (sorted position order) = glu(rstd * x @ w13[e]^T)
+void launch_moe_glu(const bf16_t* x, long ldx, const bf16_t* w13, const int* ids, const float* rstd, int* plan,
+                    bf16_t* h, int M, int H, int I, int E, int k, int tm, hipStream_t s);
+// y [M, H] = residual + sum_j bf16(wts * h @ w2[e]^T); yslot: [s_cap, H] bf16, or with splits > 1 [splits, s_cap, H]
+// fp32 slabs that the combine sums in slab order
+void launch_moe_down(const bf16_t* h, const bf16_t* w2, const int* plan, const float* wts, void* yslot,
+                     const bf16_t* residual, long ldr, bf16_t* y, int M, int H, int I, int E, int k, int tm,
+                     int splits, hipStream_t s);
 }  // namespace shai

@@ -688,6 +688,17 @@ class LLMEngine:
         if self.speculative is not None and self.mcfg is not None:
             raise NotImplementedError("speculative decoding is not supported yet for multimodal (mllama) models: the "
                                       "verify step has no image cross-attention path")
+        text_cfg = self.mcfg.text if self.mcfg is not None else cfg
+        if getattr(text_cfg, "num_local_experts", 0) > 0:  # sparse mixture of experts (Mixtral): MoEMLP layers
+            if self.mcfg is not None:
+                raise NotImplementedError("mixture-of-experts text towers are not supported for multimodal (mllama) "
+                                          "models: the cross-attention layers' MLP is dense only")
+            if tp().size > 1:
+                raise NotImplementedError("tensor parallelism is not supported yet for mixture-of-experts models: "
+                                          "the expert weights are not sharded")
+            if (quantization or "").lower() not in ("", "none", "bf16"):
+                raise NotImplementedError(f"quantization={quantization!r} is not supported yet for mixture-of-experts "
+                                          "models: the grouped expert GEMMs read bf16 weights only")
         if self.kv_fp8 and not (k_scale > 0 and v_scale > 0 and math.isfinite(k_scale) and math.isfinite(v_scale)):
             raise ValueError(f"k_scale / v_scale must be positive and finite, got {k_scale}, {v_scale}")
         if self.mcfg is not None:
@@ -747,6 +758,15 @@ class LLMEngine:
             scratch_bytes = 2 * self.kv_scratch_blocks * hk * KV_BLOCK * cfg.head_dim * 2
             buf = torch.empty(shape, dtype=torch.bfloat16, device=self.device)
             self.kv_scratch = (buf[0], buf[1])
+        # mixture of experts: h, the slot outputs and the plan of the largest step (one layer at a time, shared by every
+        # layer), allocated here so that it is out of the free memory the block pool below is sized from
+        self.moe_scratch = None
+        if cfg.num_local_experts > 0 and self.device.type == "cuda":
+            self.moe_scratch = ops.MoEScratch(prefill_token_budget + max_num_seqs, cfg.hidden_size,
+                                              cfg.intermediate_size, cfg.num_local_experts, cfg.num_experts_per_tok,
+                                              self.device)
+            for layer in self.model.layers:
+                layer.mlp.scratch = self.moe_scratch
         self.kv_blocks_budget = None   # blocks the memory budget allows, before the cap by what max_num_seqs can use
         if num_kv_blocks is None:
             if self.device.type == "cuda":

@@ -59,10 +59,25 @@ class LlamaConfig:
     bos_token_id: int = 1
     eos_token_id: int = 2
     rope_scaling: Optional[dict] = None
+    # sparse mixture of experts (Mixtral): 0 = dense, every layer's mlp a LlamaMLP; > 0 = that many experts per
+    # layer, each token through the num_experts_per_tok the router picks (MoEMLP)
+    num_local_experts: int = 0
+    num_experts_per_tok: int = 2
 
     @staticmethod
     def mistral_7b():
         return LlamaConfig()
+
+    @staticmethod
+    def mixtral_8x7b():
+        """Mixtral-8x7B: Mistral-7B's shape, 8 experts per layer, top-2."""
+        return LlamaConfig(vocab_size=32000, rope_theta=1e6, num_local_experts=8, num_experts_per_tok=2)
+
+    @staticmethod
+    def tiny_moe():
+        c = LlamaConfig.tiny()
+        c.num_local_experts, c.num_experts_per_tok = 8, 2
+        return c
 
     @staticmethod
     def llama3_8b():
@@ -111,7 +126,9 @@ class LlamaConfig:
                            bos_token_id=d.get("bos_token_id", 1) or 1,
                            eos_token_id=(d.get("eos_token_id", 2) if not isinstance(d.get("eos_token_id"), list)
                                          else d["eos_token_id"][0]),
-                           rope_scaling=d.get("rope_scaling"))
+                           rope_scaling=d.get("rope_scaling"),
+                           num_local_experts=d.get("num_local_experts", 0) or 0,
+                           num_experts_per_tok=d.get("num_experts_per_tok", 2) or 2)
 
 
 def rope_tables(cfg: LlamaConfig, max_pos: int, device) -> tuple:
@@ -244,13 +261,34 @@ class LlamaMLP(nn.Module):
         return self.down_proj(self.gate_up_proj(x, rms_eps=rms_eps), residual=residual)
 
 
+class MoEMLP(nn.Module):
+    """Sparse mixture-of-experts MLP (Mixtral's block_sparse_moe): ``gate`` [E, H] routes every row to
+    ``num_experts_per_tok`` of the E experts; ``w13`` [E, 2 I, H] holds each expert's up (w3) and gate (w1) rows
+    interleaved (value, gate) as ``GLULinear.interleave`` lays out the dense MLP; ``w2`` [E, H, I].  The router weight
+    is fp32: 128 KB per layer at Mixtral size, and folding the norm gain into it then adds no rounding to the routing
+    decision.  Not tensor-parallel (the engine rejects TP > 1)."""
+
+    def __init__(self, cfg: LlamaConfig):
+        super().__init__()
+        E, H, I = cfg.num_local_experts, cfg.hidden_size, cfg.intermediate_size
+        self.k = cfg.num_experts_per_tok
+        self.gate = nn.Parameter(torch.empty(E, H, dtype=torch.float32), requires_grad=False)
+        self.w13 = nn.Parameter(torch.empty(E, 2 * I, H, dtype=torch.bfloat16), requires_grad=False)
+        self.w2 = nn.Parameter(torch.empty(E, H, I, dtype=torch.bfloat16), requires_grad=False)
+        self.scratch = None   # the engine's ops.MoEScratch, shared by all layers; None: every call allocates
+
+    def forward(self, x, residual=None, rms_eps=None):
+        return ops.moe_mlp(x, self.gate, self.w13, self.w2, self.k, rms_eps=rms_eps, residual=residual,
+                           scratch=self.scratch)
+
+
 class LlamaDecoderLayer(nn.Module):
     def __init__(self, cfg: LlamaConfig):
         super().__init__()
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
         self.self_attn = LlamaAttention(cfg)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps)
-        self.mlp = LlamaMLP(cfg)
+        self.mlp = MoEMLP(cfg) if cfg.num_local_experts > 0 else LlamaMLP(cfg)
 
     def forward(self, x, batch, kc, vc, cos, sin, folded: bool = False):
         if folded:  # norm gains live in the qkv / gate_up weights; RMS scaling fused into those GEMMs
@@ -290,7 +328,13 @@ class LlamaForCausalLM(nn.Module):
             norm.weight.fill_(1.0)
         for layer in self.layers:
             fold(layer.self_attn.qkv_proj.weight, layer.input_layernorm)
-            fold(layer.mlp.gate_up_proj.weight, layer.post_attention_layernorm)
+            if isinstance(layer.mlp, MoEMLP):  # both consumers of the norm, then the gain is reset (by the last)
+                g = layer.post_attention_layernorm.weight.float()
+                layer.mlp.gate.mul_(g[None, :])
+                layer.mlp.w13.copy_((layer.mlp.w13.float() * g[None, None, :]).to(layer.mlp.w13.dtype))
+                layer.post_attention_layernorm.weight.fill_(1.0)
+            else:
+                fold(layer.mlp.gate_up_proj.weight, layer.post_attention_layernorm)
         fold(self.lm_head.weight, self.norm)
         self._folded = True
 
@@ -337,7 +381,27 @@ class LlamaForCausalLM(nn.Module):
             gk, uk = p + "mlp.gate_proj.weight", p + "mlp.up_proj.weight"
             if gk in out and uk in out:
                 out[p + "mlp.gate_up_proj.weight"] = GLULinear.interleave(out.pop(uk), out.pop(gk))
+            self._convert_moe_keys(out, p)
         return out
+
+    def _convert_moe_keys(self, out: dict, p: str):
+        """Mixtral's expert weights of layer prefix ``p`` -> mlp.gate / mlp.w13 / mlp.w2.  Two layouts: the hub's
+        (block_sparse_moe.gate, block_sparse_moe.experts.{e}.w1 (gate) / w3 (up) / w2 (down)) and the fused tensors of
+        recent transformers (mlp.gate.weight, mlp.experts.gate_up_proj [E, 2 I, H] = [gate; up], mlp.experts.down_proj)."""
+        E = self.cfg.num_local_experts
+        hub = p + "block_sparse_moe."
+        if hub + "gate.weight" in out:
+            out[p + "mlp.gate"] = out.pop(hub + "gate.weight")
+            w1 = [out.pop(f"{hub}experts.{e}.w1.weight") for e in range(E)]
+            w3 = [out.pop(f"{hub}experts.{e}.w3.weight") for e in range(E)]
+            out[p + "mlp.w13"] = torch.stack([GLULinear.interleave(u, g) for u, g in zip(w3, w1)])
+            out[p + "mlp.w2"] = torch.stack([out.pop(f"{hub}experts.{e}.w2.weight") for e in range(E)])
+        elif p + "mlp.experts.gate_up_proj" in out:
+            out[p + "mlp.gate"] = out.pop(p + "mlp.gate.weight")
+            gu = out.pop(p + "mlp.experts.gate_up_proj")
+            I = gu.shape[1] // 2
+            out[p + "mlp.w13"] = torch.stack([gu[:, I:], gu[:, :I]], dim=2).reshape(gu.shape)
+            out[p + "mlp.w2"] = out.pop(p + "mlp.experts.down_proj")
 
 
 def allocate_kv_cache(cfg: LlamaConfig, kv_heads_local: int, num_blocks: int, device, dtype=torch.bfloat16):

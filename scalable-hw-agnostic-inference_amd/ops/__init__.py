@@ -31,6 +31,7 @@ __all__ = [
     "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE", "resolve_kv_prefill", "KV_PREFILL_ROUTES",
     "sample_penalized", "penalty_state_init", "token_logprobs", "LOGPROBS_MAX",
     "sample_constrained", "constraint_state_init",
+    "moe_route", "moe_experts_glu", "moe_experts_down", "moe_mlp", "MoEPlan", "MoEScratch",
 ]
 
 
@@ -1241,3 +1242,121 @@ def embedding(ids, table):
     out = torch.empty(*ids.shape, table.shape[1], dtype=table.dtype, device=table.device)
     _K().embedding(_i32(ids).contiguous(), table, out)
     return out
+
+
+# ----------------------------------------------------------------------------- sparse mixture of experts (Mixtral)
+@dataclass
+class MoEPlan:
+    """The alignment record between ``moe_experts_glu`` and ``moe_experts_down`` (opaque to callers).  GPU: ``buf``
+    holds the tile count, each tile's expert, the slots sorted by expert (slot = m k + j, padded per expert to
+    ``tile_rows`` with -1) and the position of every slot; ``h`` has ``s_cap`` rows in that order.  CPU: ``buf`` is
+    None and ``h`` is in slot order."""
+    ids: torch.Tensor
+    M: int
+    k: int
+    E: int
+    buf: Optional[torch.Tensor] = None
+    tile_rows: int = 0
+    s_cap: int = 0
+
+    @property
+    def pos(self) -> torch.Tensor:
+        """int32 [M, k]: the row of ``h`` that holds slot (m, j) (-1: its expert id was out of range)."""
+        S = self.M * self.k
+        if self.buf is None:
+            return torch.arange(S, dtype=torch.int32, device=self.ids.device).view(self.M, self.k)
+        return self.buf[self.buf.numel() - S:].view(self.M, self.k)
+
+
+def _moe_check(name: str, H: int, I: int, E: int, k: int):
+    if not (2 <= E <= 16 and k in (1, 2) and H >= 64 and I >= 64 and H % 64 == 0 and I % 64 == 0):
+        raise ValueError(f"{name}: needs 2 <= E <= 16, k in (1, 2), H % 64 == 0 and I % 64 == 0; got E={E} k={k} "
+                         f"H={H} I={I}")
+
+
+class MoEScratch:
+    """One engine's buffers for ``moe_mlp`` steps of up to ``max_rows`` rows (h, the slot outputs, the plan), shared by
+    every layer: allocated once, so a step allocates nothing but its output."""
+
+    def __init__(self, max_rows: int, H: int, I: int, E: int, k: int, device):
+        self.max_rows, self.key = max_rows, (H, I, E, k)
+        # (the row-tile height and the split count change with M: the largest need is at one of these row counts)
+        dims = [_K().moe_dims(M, I, E, k, 0, 0) for M in {1, 2, min(31, max_rows), max_rows}]
+        self.h = torch.empty(max(d[1] for d in dims) * I, dtype=torch.bfloat16, device=device)
+        self.y = torch.empty(max(d[1] * H * (4 * d[3] if d[3] > 1 else 2) for d in dims), dtype=torch.uint8,
+                             device=device)
+        self.plan = torch.empty(max(d[2] for d in dims), dtype=torch.int32, device=device)
+
+    def views(self, M: int, H: int, I: int, E: int, k: int):
+        """(plan words, h, yslot) for a step of M rows; None when the step does not fit (the ops then allocate)."""
+        if M > self.max_rows or (H, I, E, k) != self.key:
+            return None
+        _, s_cap, words, ns = _K().moe_dims(M, I, E, k, 0, 0)
+        y = (self.y[:ns * s_cap * H * 4].view(torch.float32).view(ns, s_cap, H) if ns > 1 else
+             self.y[:s_cap * H * 2].view(torch.bfloat16).view(s_cap, H))
+        return self.plan[:words], self.h[:s_cap * I].view(s_cap, I), y
+
+
+def moe_route(x, wg, k: int, rms_eps: Optional[float] = None):
+    """Top-k routing of x [M, H] against the router weight wg [E, H] (fp32): (ids int32 [M, k], weights fp32 [M, k],
+    rstd fp32 [M]).  logit = rstd * <x, wg_e> with rstd = rsqrt(mean(x^2) + rms_eps) (1 without rms_eps); the k largest
+    win, a tie goes to the lower expert index; weights = softmax over the winners."""
+    M, H = x.shape
+    E = wg.shape[0]
+    _moe_check("moe_route", H, 64, E, int(k))
+    if not _gpu(x):
+        return ref.moe_route(x, wg, int(k), rms_eps)
+    ids = torch.empty(M, int(k), dtype=torch.int32, device=x.device)
+    weights = torch.empty(M, int(k), dtype=torch.float32, device=x.device)
+    rstd = torch.empty(M, dtype=torch.float32, device=x.device)
+    wg32 = wg if wg.dtype == torch.float32 else wg.float()
+    _K().moe_route(x, wg32.contiguous(), ids, weights, rstd, -1.0 if rms_eps is None else float(rms_eps))
+    return ids, weights, rstd
+
+
+def moe_experts_glu(x, w13, ids, rstd=None, tile_rows: Optional[int] = None, h: Optional[torch.Tensor] = None,
+                    plan_buf: Optional[torch.Tensor] = None):
+    """The routed experts' first GEMM: h = bf16(v * silu(g)) with (v, g) = rstd * x @ w13[e]^T de-interleaved, for
+    every slot (m, j) with e = ids[m, j]; w13 [E, 2 I, H] rows interleaved (value, gate).  Returns (h, plan): h's row
+    order belongs to the plan.  ``tile_rows`` (32 / 128) forces the row-tile height; ``h`` / ``plan_buf`` supply the buffers."""
+    M, H = x.shape
+    E, I = w13.shape[0], w13.shape[1] // 2
+    k = ids.shape[1]
+    _moe_check("moe_experts_glu", H, I, E, k)
+    if not _gpu(x):
+        return ref.moe_experts_glu(x, w13, ids, rstd), MoEPlan(ids, M, k, E)
+    tm, s_cap, words, _ = _K().moe_dims(M, I, E, k, int(tile_rows or 0), 0)
+    buf = plan_buf if plan_buf is not None else torch.empty(words, dtype=torch.int32, device=x.device)
+    if h is None:
+        h = torch.empty(s_cap, I, dtype=torch.bfloat16, device=x.device)
+    ids = _i32(ids).contiguous()
+    _K().moe_glu(x, w13, ids, rstd, buf, h, tm)
+    return h, MoEPlan(ids, M, k, E, buf, tm, s_cap)
+
+
+def moe_experts_down(h, w2, plan: MoEPlan, weights, residual=None, splits: Optional[int] = None,
+                     yslot: Optional[torch.Tensor] = None):
+    """y [M, H] = bf16(residual + sum_j bf16(weights[m, j] * h[m, j] @ w2[e_j]^T)), j ascending; w2 [E, H, I].
+    ``splits`` forces the K split of the GEMM (default: from M); ``yslot`` supplies the slot-output buffer
+    ([s_cap, H] bf16, with splits > 1 [splits, s_cap, H] fp32)."""
+    E, H, I = w2.shape
+    _moe_check("moe_experts_down", H, I, E, plan.k)
+    if not _gpu(h):
+        return ref.moe_experts_down(h, w2, plan.ids, weights, residual)
+    _, _, _, ns = _K().moe_dims(plan.M, I, E, plan.k, plan.tile_rows, int(splits or 0))
+    if yslot is None:
+        yslot = (torch.empty(ns, plan.s_cap, H, dtype=torch.float32, device=h.device) if ns > 1 else
+                 torch.empty(plan.s_cap, H, dtype=torch.bfloat16, device=h.device))
+    y = torch.empty(plan.M, H, dtype=torch.bfloat16, device=h.device)
+    _K().moe_down(h, w2, plan.buf, weights, yslot, residual, y, plan.tile_rows, ns)
+    return y
+
+
+def moe_mlp(x, wg, w13, w2, k: int, rms_eps: Optional[float] = None, residual=None,
+            scratch: Optional[MoEScratch] = None):
+    """The whole sparse MLP: route, the experts' GLU GEMM, the down GEMM and the weighted combine (+ residual)."""
+    ids, weights, rstd = moe_route(x, wg, k, rms_eps)
+    v = scratch.views(x.shape[0], x.shape[1], w2.shape[2], w2.shape[0], k) if scratch is not None and _gpu(x) else None
+    buf, hbuf, yslot = v if v is not None else (None, None, None)
+    h, plan = moe_experts_glu(x, w13, ids, rstd if rms_eps is not None else None, h=hbuf, plan_buf=buf)
+    return moe_experts_down(h, w2, plan, weights, residual, yslot=yslot)

@@ -966,3 +966,51 @@ def sample_constrained(logits, temps, top_k, top_p, uniforms, state, rows, rep, 
             penalty_state_add(state, rows, toks)
         con_advance(cstate, crows, toks)
     return toks
+
+
+# ----------------------------------------------------------------------------- sparse mixture of experts (Mixtral)
+def moe_route(x, wg, k: int, rms_eps=None):
+    xf = x.float()
+    rstd = (torch.rsqrt(xf.pow(2).mean(-1) + rms_eps) if rms_eps is not None
+            else torch.ones(x.shape[0], dtype=torch.float32, device=x.device))
+    logits = (xf @ wg.float().t()) * rstd[:, None]
+    ids, vals, rest = [], [], logits.clone()
+    for _ in range(k):  # argmax returns the first of equal maxima: a tie goes to the lower expert index
+        i = rest.argmax(dim=1, keepdim=True)
+        ids.append(i)
+        vals.append(rest.gather(1, i))
+        rest.scatter_(1, i, float("-inf"))
+    ids, vals = torch.cat(ids, 1), torch.cat(vals, 1)
+    w = torch.exp(vals - vals[:, :1])
+    return ids.to(torch.int32), w / w.sum(1, keepdim=True), rstd
+
+
+def moe_experts_glu(x, w13, ids, rstd=None):
+    """h [M k, I] in slot order (slot = m k + j), rounded to x's dtype."""
+    M, k = ids.shape
+    xf = x.float()
+    h = torch.zeros(M * k, w13.shape[1] // 2, dtype=torch.float32, device=x.device)
+    flat = ids.reshape(-1).long()
+    for e in flat.unique().tolist():
+        s = (flat == e).nonzero().squeeze(1)
+        z = xf[s // k] @ w13[e].float().t()
+        if rstd is not None:
+            z = z * rstd.float()[s // k, None]
+        h[s] = z[:, 0::2] * torch.nn.functional.silu(z[:, 1::2])
+    return h.to(x.dtype)
+
+
+def moe_experts_down(h, w2, ids, weights, residual=None):
+    M, k = ids.shape
+    o = torch.zeros(M * k, w2.shape[1], dtype=torch.float32, device=h.device)
+    flat = ids.reshape(-1).long()
+    wf = weights.float().reshape(-1)
+    for e in flat.unique().tolist():
+        s = (flat == e).nonzero().squeeze(1)
+        o[s] = ((h[s].float() @ w2[e].float().t()) * wf[s, None]).to(h.dtype).float()
+    y = o.view(M, k, -1)[:, 0]
+    for j in range(1, k):
+        y = y + o.view(M, k, -1)[:, j]
+    if residual is not None:
+        y = residual.float() + y
+    return y.to(h.dtype)
