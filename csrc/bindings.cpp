@@ -628,6 +628,28 @@ bool kv8_cache(const Tensor& k_cache, const Tensor& v_cache, double k_scale, dou
              "k_scale / v_scale must be positive and finite");
   return true;
 }
+// MXFP4 KV cache: both caches uint8, contiguous [blocks, Hkv, 64, D/2 + D/32] -- per (block, KV head) one region
+// of 64 * D/2 code bytes followed by 64 * D/32 e8m0 scale bytes (the last two dims only spell the region's size) --
+// D 64 or 128, no scalar scales.  Returns false when neither cache is uint8; a mixed pair is an error.
+bool kv4_cache(const Tensor& k_cache, const Tensor& v_cache, double k_scale, double v_scale) {
+  const bool k4 = k_cache.scalar_type() == at::kByte, v4 = v_cache.scalar_type() == at::kByte;
+  SHAI_CHECK(k4 == v4, "k_cache / v_cache dtypes differ (", k_cache.scalar_type(), " vs ", v_cache.scalar_type(),
+             "): an mxfp4 KV cache needs both as uint8");
+  if (!k4) return false;
+  SHAI_CHECK(k_cache.is_cuda() && v_cache.is_cuda(), "mxfp4 KV cache must be on the GPU");
+  SHAI_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 64 && v_cache.sizes() == k_cache.sizes() &&
+                 (k_cache.size(3) == 34 || k_cache.size(3) == 68),
+             "mxfp4 KV cache must be [blocks, Hkv, 64, D/2 + D/32] with D 64 or 128");
+  SHAI_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous(), "mxfp4 KV cache must be contiguous");
+  SHAI_CHECK(reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 16 == 0 &&
+                 reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 16 == 0, "mxfp4 KV cache must be 16-byte aligned");
+  SHAI_CHECK(k_scale == 1.0 && v_scale == 1.0, "an mxfp4 KV cache has group scales only: k_scale / v_scale must be 1");
+  return true;
+}
+// head dim of a cache tensor: its last dim, or for an mxfp4 cache (uint8) the D of its D/2 + D/32 bytes per row
+int64_t kv_head_dim(const Tensor& cache) {
+  return cache.scalar_type() == at::kByte ? cache.size(3) * 32 / 17 : cache.size(3);
+}
 uint8_t* u8ptr(const Tensor& t) { return reinterpret_cast<uint8_t*>(t.data_ptr()); }
 void kv8_scales(shai::DecodeAttnArgs& a, double k_scale, double v_scale) {
   a.k_scale = (float)k_scale;
@@ -1533,8 +1555,9 @@ void paged_attn_varlen(const Tensor& q, const Tensor& k_cache, const Tensor& v_c
 void decode_attn_launch(shai::DecodeAttnArgs& a, const Tensor& k_cache, const Tensor& v_cache,
                         const Tensor& block_table, const Tensor& ctx_lens, const Tensor& ws, int64_t num_splits,
                         double scale, double k_scale, double v_scale) {
-  a.kv_fp8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
-  if (!a.kv_fp8) {
+  a.kv_fp4 = kv4_cache(k_cache, v_cache, k_scale, v_scale);
+  a.kv_fp8 = !a.kv_fp4 && kv8_cache(k_cache, v_cache, k_scale, v_scale);
+  if (!a.kv_fp8 && !a.kv_fp4) {
     check_bf16(k_cache, "k_cache");
     check_bf16(v_cache, "v_cache");
   }
@@ -1547,7 +1570,7 @@ void decode_attn_launch(shai::DecodeAttnArgs& a, const Tensor& k_cache, const Te
   const int G = a.Hq / a.Hkv;
   SHAI_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "decode_attn supports GQA groups Hq / Hkv of 1, 2, 4 and 8, got ",
              G);
-  SHAI_CHECK(k_cache.size(3) == a.D, "decode_attn: cache head dim != q head dim");
+  SHAI_CHECK(kv_head_dim(k_cache) == a.D, "decode_attn: cache head dim != q head dim");
   a.k_cache = k_cache.data_ptr();
   a.v_cache = v_cache.data_ptr();
   a.block_table = block_table.data_ptr<int>();
@@ -1687,7 +1710,7 @@ void decode_attn_rope(const Tensor& qkv, const Tensor& k_cache, const Tensor& v_
                  sin.is_contiguous(), "rope tables: contiguous fp32");
   SHAI_CHECK(k_cache.dim() == 4 && k_cache.size(2) == 64 && k_cache.size(1) == hk, "decode_attn_rope cache shape");
   shai::DecodeAttnArgs a{};
-  a.D = k_cache.size(3);
+  a.D = kv_head_dim(k_cache);
   a.B = part ? o.size(0) : qkv.size(0);
   a.Hq = h;
   a.Hkv = hk;
@@ -1734,6 +1757,16 @@ void kv_write(const Tensor& k, const Tensor& v, const Tensor& k_cache, const Ten
   check_rows(k, "k");
   check_rows(v, "v");
   check_i32(slots, "slots");
+  if (kv4_cache(k_cache, v_cache, k_scale, v_scale)) {
+    SHAI_CHECK(k.dim() == 3 && v.sizes() == k.sizes() && k.size(1) == k_cache.size(1) &&
+                   k.size(2) == kv_head_dim(k_cache),
+               "k / v [T, Hkv, D] must match the mxfp4 cache [blocks, Hkv, 64, D/2 + D/32]");
+    SHAI_CHECK(k.stride(1) == k.size(2) && v.stride(1) == v.size(2), "packed heads");
+    SHAI_CHECK(slots.numel() == k.size(0), "slots must have T entries");
+    shai::launch_kv_write_f4(cptr(k), cptr(v), u8ptr(k_cache), u8ptr(v_cache), slots.data_ptr<int>(), k.size(0),
+                             k.size(1), k.size(2), k.stride(0), v.stride(0), stream());
+    return;
+  }
   if (kv8_cache(k_cache, v_cache, k_scale, v_scale)) {
     SHAI_CHECK(k.dim() == 3 && v.sizes() == k.sizes() && k.size(1) == k_cache.size(1) && k.size(2) == k_cache.size(3),
                "k / v [T, Hkv, D] must match the cache [blocks, Hkv, 64, D]");
@@ -1819,8 +1852,9 @@ void rope_qkv_cache(const Tensor& qkv, const Tensor& positions, const Tensor& co
                     const Tensor& k_cache, const Tensor& v_cache, const Tensor& slots, int64_t H, int64_t Hkv,
                     double k_scale, double v_scale) {
   check_bf16(qkv, "qkv");
-  const bool f8 = kv8_cache(k_cache, v_cache, k_scale, v_scale);
-  if (!f8) {
+  const bool f4 = kv4_cache(k_cache, v_cache, k_scale, v_scale);
+  const bool f8 = !f4 && kv8_cache(k_cache, v_cache, k_scale, v_scale);
+  if (!f8 && !f4) {
     check_bf16(k_cache, "k_cache");
     check_bf16(v_cache, "v_cache");
   }
@@ -1832,11 +1866,17 @@ void rope_qkv_cache(const Tensor& qkv, const Tensor& positions, const Tensor& co
   SHAI_CHECK(k_cache.dim() == 4 && k_cache.is_contiguous() && v_cache.is_contiguous() && k_cache.size(1) == Hkv &&
                  k_cache.size(2) == 64,
              "caches must be contiguous [blocks, Hkv, 64, D]");
-  const int D = k_cache.size(3);
+  const int D = kv_head_dim(k_cache);
   SHAI_CHECK(D % 16 == 0 && qkv.size(1) == (H + 2 * Hkv) * D, "qkv width / head dim mismatch");
   SHAI_CHECK(cos.size(-1) == D / 2, "cos/sin must be [max_pos, D/2] (full-dim NeoX rotation)");
   const int T = qkv.size(0);
   SHAI_CHECK(positions.numel() == T && slots.numel() == T, "positions / slots must have T entries");
+  if (f4) {
+    shai::launch_rope_qkv_cache_f4(mptr(qkv), qkv.stride(0), positions.data_ptr<int>(), cos.data_ptr<float>(),
+                                   sin.data_ptr<float>(), u8ptr(k_cache), u8ptr(v_cache), slots.data_ptr<int>(), T, H,
+                                   Hkv, D, stream());
+    return;
+  }
   if (f8) {
     shai::launch_rope_qkv_cache_f8(mptr(qkv), qkv.stride(0), positions.data_ptr<int>(), cos.data_ptr<float>(),
                                    sin.data_ptr<float>(), u8ptr(k_cache), u8ptr(v_cache), slots.data_ptr<int>(), T, H,
@@ -1853,15 +1893,23 @@ void rope_qkv_cache(const Tensor& qkv, const Tensor& positions, const Tensor& co
 // remapped to scratch indices.
 void kv_dequant_blocks(const Tensor& k_cache, const Tensor& v_cache, const Tensor& phys, const Tensor& k_out,
                        const Tensor& v_out, double k_scale, double v_scale) {
-  SHAI_CHECK(kv8_cache(k_cache, v_cache, k_scale, v_scale), "kv_dequant_blocks: the caches must be float8_e4m3fn");
+  const bool f4 = kv4_cache(k_cache, v_cache, k_scale, v_scale);
+  SHAI_CHECK(f4 || kv8_cache(k_cache, v_cache, k_scale, v_scale),
+             "kv_dequant_blocks: the caches must be float8_e4m3fn or an mxfp4 (uint8) pair");
   check_bf16(k_out, "k_out");
   check_bf16(v_out, "v_out");
   check_i32(phys, "phys");
   SHAI_CHECK(k_out.dim() == 4 && k_out.is_contiguous() && v_out.is_contiguous() && v_out.sizes() == k_out.sizes() &&
-                 k_out.size(1) == k_cache.size(1) && k_out.size(2) == 64 && k_out.size(3) == k_cache.size(3),
+                 k_out.size(1) == k_cache.size(1) && k_out.size(2) == 64 && k_out.size(3) == kv_head_dim(k_cache),
              "scratch must be contiguous bf16 [capacity, Hkv, 64, D] matching the cache");
   SHAI_CHECK(phys.dim() == 1 && phys.numel() <= k_out.size(0), "kv_dequant_blocks: ", phys.numel(),
              " blocks do not fit the scratch capacity ", k_out.size(0));
+  if (f4) {
+    shai::launch_kv_dequant_blocks_f4(u8ptr(k_cache), u8ptr(v_cache), phys.data_ptr<int>(), (int)phys.numel(),
+                                      (int)k_cache.size(1), (int)kv_head_dim(k_cache), mptr(k_out), mptr(v_out),
+                                      stream());
+    return;
+  }
   shai::launch_kv_dequant_blocks(u8ptr(k_cache), u8ptr(v_cache), phys.data_ptr<int>(), (int)phys.numel(),
                                  k_cache.size(1) * 64 * k_cache.size(3), mptr(k_out), mptr(v_out), (float)k_scale,
                                  (float)v_scale, stream());

@@ -39,7 +39,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 
 KERNEL_SRCS = ["kernels/norm.hip", "kernels/gemm.hip", "kernels/gemm_lds.hip", "kernels/gemm_8ph.hip", "kernels/gemm_w4.hip", "kernels/gemm_ws.hip", "kernels/conv_halo.hip", "kernels/attention.hip", "kernels/attention2.hip", "kernels/attention3.hip", "kernels/elementwise.hip", "kernels/dit.hip",
                "kernels/sampling.hip", "kernels/gemv.hip", "kernels/gemv2.hip", "kernels/gemv_fp4.hip", "kernels/gemv_nf4.hip",
-               "kernels/gemm_f8.hip", "kernels/attention_kv8.hip", "kernels/gemm_fp4.hip",
+               "kernels/gemm_f8.hip", "kernels/attention_kv8.hip", "kernels/attention_kv4.hip", "kernels/gemm_fp4.hip",
                "kernels/attention_spec.hip", "kernels/gemm_nf4.hip", "kernels/moe.hip"]
 # kernels that must not spill, as source -> part of the kernel's mangled name: the source is compiled with the
 # resource-usage remarks on, and build() fails when one of the named kernels reports scratch (the fp8-cache
@@ -48,6 +48,10 @@ KERNEL_SRCS = ["kernels/norm.hip", "kernels/gemm.hip", "kernels/gemm_lds.hip", "
 NO_SCRATCH = {"kernels/attention.hip": "decode_attn_kernelINS_5KvFp8",
               # the native fp8 paged prefill attention (flash_v1.h's body with the fp8 format, D = 64 and 128)
               "kernels/attention_kv8.hip": "flash_fwd_kernelINS_5KvFp8",
+              # the MXFP4-cache instantiations of the split decode kernel (16 converts per K chunk beside the ring
+              # bookkeeping) and the 4-bit cache writers / widener
+              "kernels/attention_kv4.hip": ("decode_attn_kernelINS_5KvFp4", "kv_write_f4_kernel",
+                                            "rope_qkv_cache_f4_kernel", "kv_dequant_blocks_f4_kernel"),
               # the fp4 tile GEMM holds up to 128 accumulators beside the widened fragments: every instantiation
               "kernels/gemm_fp4.hip": "gemm_fp4_kernel",
               # the samplers (plain, penalised, constrained) and the log-probability kernel: every instantiation
@@ -76,6 +80,7 @@ EXTRA_KFLAGS = {"kernels/attention3.hip": "-mllvm -amdgpu-mfma-vgpr-form -fno-sl
                 # products per step come out as 64 v_mul_f32 either way of counting (profiles/nf4_decode.md)
                 "kernels/gemv_nf4.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops",
                 "kernels/gemm_nf4.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops",
+                "kernels/attention_kv4.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops",
                 "kernels/moe.hip": "-Xclang -target-feature -Xclang -packed-fp32-ops",
                 "kernels/gemm_ws.hip": "-mllvm -pragma-unroll-threshold=100000 -fno-slp-vectorize",
                 "kernels/conv_halo.hip": "-mllvm -pragma-unroll-threshold=100000 -fno-slp-vectorize"}

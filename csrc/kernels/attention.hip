@@ -713,7 +713,7 @@ static void launch_decode_split(const DecodeAttnArgs& a, dim3 grid, int G, hipSt
 void launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
   const int G = a.Hq / a.Hkv;
   // wave-per-block short-context kernel (bf16 cache only: an fp8 cache always takes the split kernel)
-  if (!a.kv_fp8 && a.D == 128 && G == kWbG && a.num_splits == 1 && decode_wb_mode()) {
+  if (!a.kv_fp8 && !a.kv_fp4 && a.D == 128 && G == kWbG && a.num_splits == 1 && decode_wb_mode()) {
     decode_attn_wb_kernel<<<dim3((unsigned)(a.B * a.Hkv)), kWbG * 64, kWbLds, s>>>(a);
     return;
   }
@@ -733,7 +733,9 @@ void launch_decode_attn(const DecodeAttnArgs& a, hipStream_t s) {
   const long items = (long)a.B * a.Hkv * a.num_splits;
   const bool persist = force >= 0 ? force == 1 : a.num_splits > 8;
   const dim3 grid((unsigned)(persist ? std::min<long>(items, width) : items));
-  if (a.kv_fp8) {
+  if (a.kv_fp4) {  // MXFP4 cache: the split kernel's KvFp4 instantiations (attention_kv4.hip)
+    launch_decode_split_kv4(a, grid.x, s);
+  } else if (a.kv_fp8) {
     if (a.D == 128) launch_decode_split<KvFp8, 128>(a, grid, G, s);
     else launch_decode_split<KvFp8, 64>(a, grid, G, s);
   } else {

@@ -1,6 +1,7 @@
-// The split paged decode attention kernel (one query token per sequence), written once for both cache storage
-// formats, and the pieces it shares with the wave-per-block kernel of attention.hip and the fp8 cache writers of
-// attention_kv8.hip.
+// The split paged decode attention kernel (one query token per sequence), written once for the three cache storage
+// formats (bf16, fp8, MXFP4), and the pieces it shares with the wave-per-block kernel of attention.hip and the cache
+// writers of attention_kv8.hip (fp8) and attention_kv4.hip (MXFP4, which also holds the launch of the KvFp4
+// instantiations).
 #pragma once
 #include "common.h"
 #include "launchers.h"
@@ -58,11 +59,16 @@ __device__ __forceinline__ kv8_f32x2 kv8_dq2(uint32_t codes) {
 // score loop's lane = key reads undo it); qk adds one 16-byte K chunk times the matching q elements to the two
 // score chains; pv2 (D = 128) adds one key pair times this lane's two output dims; v_f32 (D = 64) widens one V
 // element.  new_k / new_v give this step's token after the rounding the cache applies -- the values attended --
-// and store_k / store_v are what wave 0 writes.  kMaxThreads is the wrapper's launch bound.
+// and store_k / store_v are what wave 0 writes.  kMaxThreads is the wrapper's launch bound.  kSlot is a ring slot
+// in elements.  kMx marks a format with a per-group scale plane (KvFp4 below): its slot layout, DMA instruction list,
+// per-chunk scale in qk / pv2 and cross-lane new-token quantisation take the body's `if constexpr (Fmt::kMx)`
+// branches; the two formats here compile to the code they compiled to without them.
 // ----------------------------------------------------------------------------
 template <int D>
 struct KvBf16 {
   typedef bf16_t E;
+  static constexpr bool kMx = false;          // no per-group scale plane
+  static constexpr int kSlot = 2 * 64 * D;    // elements per ring slot (K then V)
   static constexpr int EPC = 8, CPR = D / 8, RPI = 1024 / (2 * D);
   static constexpr int kQBytes = 8 * D * 4;   // the q rows' LDS region: sized for f32 rows, holds bf16
   // no bound given: the compiler's default of 1024 threads, a budget of 128 registers (D = 128, G = 1 spills)
@@ -138,6 +144,8 @@ struct KvBf16 {
 template <int D>
 struct KvFp8 {
   typedef uint8_t E;
+  static constexpr bool kMx = false;
+  static constexpr int kSlot = 2 * 64 * D;
   static constexpr int EPC = 16, CPR = D / 16, RPI = 1024 / D;
   static constexpr int RSH = D == 128 ? 1 : 2;   // log2 of the rows per 256-byte bank window
   static constexpr int kQBytes = 8 * D * 2;
@@ -208,6 +216,167 @@ struct KvFp8 {
 };
 
 // ----------------------------------------------------------------------------
+// MXFP4 cache codes (OCP e2m1 + one e8m0 scale byte per 32 consecutive elements of a K / V row).  One rule for every
+// writer (ops/reference.py quantize_kv_mxfp4, the weight rows' quantize_mxfp4 core, is the oracle):
+//   byte  = clamp(floor(log2(amax)) - 2 + 127, 2, 252)   (an all-zero group: 124);  value = code * 2^(byte - 127)
+//   code  = nearest e2m1 of clamp(x * 2^(127 - byte), -6, 6), ties to the even mantissa, no negative zero
+// The codes are made by explicit compares, not by v_cvt_scalef32_pk_fp4_*: the oracle never emits the code 8
+// (-0) that a hardware convert gives a small negative value, and its tie rule is written out here where a test can
+// hold it to the oracle bit for bit.  amax is taken on the integer pattern of |x| (monotone for finite values), so
+// neither the cross-lane max nor the exponent depends on the denormal mode.
+// ----------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t kv4_abs_bits(float x) { return __float_as_uint(x) & 0x7fffffffu; }
+// max of the |x| patterns over aligned groups of W lanes
+template <int W>
+__device__ __forceinline__ uint32_t kv4_group_max(uint32_t a) {
+#pragma unroll
+  for (int m = W / 2; m >= 1; m >>= 1) a = max(a, (uint32_t)__shfl_xor((int)a, m, 64));
+  return a;
+}
+__device__ __forceinline__ uint32_t kv4_scale_byte(uint32_t amax_bits) {
+  const int e = (int)(amax_bits >> 23);
+  return amax_bits == 0u ? 124u : (uint32_t)min(max(e - 2, 2), 252);
+}
+// 2^(byte - 127): the convert's scale operand and the widener's factor; 2^(127 - byte): the quantiser's factor
+__device__ __forceinline__ float kv4_scale(uint32_t byte) { return __uint_as_float(byte << 23); }
+__device__ __forceinline__ float kv4_inv(uint32_t byte) { return __uint_as_float((254u - byte) << 23); }
+__device__ __forceinline__ uint32_t kv4_code(float x, float inv) {
+  const float v = x * inv;
+  const float a = fminf(fabsf(v), 6.f);
+  const uint32_t c = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) +
+                     (uint32_t)(a >= 1.75f) + (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+  return c | ((v < 0.f && c != 0u) ? 8u : 0u);
+}
+// the code in the low nibble -> its value (exact)
+__device__ __forceinline__ float kv4_val(uint32_t code, float scale) {
+  return __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(code & 15u, scale, 0)[0];
+}
+
+// MXFP4 cache, 0.266 of the bf16 bytes.  Per (block, KV head) one contiguous region of kRegion = 64 * (D/2 + D/32)
+// bytes: the code plane (row r at r * D/2, element d in byte d/2, even d in the low nibble) and behind it the scale
+// plane (row r at 64 * D/2 + r * D/32).  One buffer descriptor covers both.  Every code * scale is a bf16 value, so
+// a chunk widens with v_cvt_scalef32_pk_bf16_fp4 (the group's 2^(byte - 127) in the scale operand) and the packed
+// bf16 dot products of the other formats stay.
+//  * a block is D/16 one-KB wave DMA instructions of codes (a quarter of bf16's) + one per scale plane: kNT = D/16
+//    + 2 instructions, dealt to the G waves round-robin; kNT is no multiple of G, so a wave issues NI or NI - 1 of
+//    them and waits on its own count;
+//  * ring slot: K codes | V codes | K scales | V scales, each scale plane in a 1 KB window: the scale instruction's
+//    lanes past the plane (D/8 chunks) take the zero-fill offset and land in the window's tail;
+//  * K rows are D/2 bytes = CPR = D/32 chunks of 16 bytes, each chunk exactly one scale group.  The lane = key
+//    score loop reads one chunk per lane per step (ds_read_b128: lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31}
+//    and the same + 32, each one LDS cycle over 64 banks = 256 B).  Row r starts at byte r * D/2, so 512 / D rows
+//    share a 256-byte bank window; the chunk XOR (r / (512 / D)) & (CPR - 1) gives the 16 lanes of every group 16
+//    different 16-byte bank quads (D = 128: the four lanes of each r & 3 class have r >> 2 = {0,3,5,6} or
+//    {1,2,4,7}, all different mod 4; D = 64: the two lanes of each r & 7 class have r >> 3 = {0,3}, {1,2}, all
+//    different mod 2).  Applied on the source side of the DMA.  The row's scale bytes are one 4- / 2-byte read at
+//    lane * D/32: consecutive addresses;
+//  * V rows stay linear.  D = 128: lane = output dim pair reads its one byte per key (64 contiguous bytes per
+//    wave) and the scale words of 8 keys as two broadcast ds_read_b128; each key's byte widens with that key's
+//    scale and v_perm regroups the two keys' bf16 pairs for the packed dot.  D = 64: lane = dim, nibble lane & 1;
+//  * rows past the context are zero-filled by the range check, codes and whole scale chunks.  A scale chunk holds
+//    16 / (D/32) rows, so the context's last chunk can carry never-written scale bytes (0xff = NaN) beside
+//    zero-filled codes: every wave zeroes those V scale bytes in LDS before its P.V (all waves write the same
+//    zeros; a wave's own lgkmcnt covers its reads).  K needs none: a key past the context has its score replaced.
+// This step's token (fused form): the owning wave takes each group's amax by a cross-lane max over the 32 (K; V at
+// D = 64) or 16 (V at D = 128) lanes that hold it, quantises, and attends the widened codes.
+template <int D>
+struct KvFp4 {
+  typedef uint8_t E;
+  static constexpr bool kMx = true;
+  static constexpr int EPC = 32, CPR = D / 32, RPI = 2048 / D;   // codes per chunk, chunks per row, rows per DMA
+  static constexpr int RSH = D == 128 ? 2 : 3;                   // log2 of the rows per 256-byte bank window
+  static constexpr int kRow = D / 2, kSclRow = D / 32;           // code / scale bytes per row
+  static constexpr int kCodes = 64 * D / 2, kRegion = 64 * (D / 2 + D / 32);
+  static constexpr int kNC = D / 32, kNT = 2 * kNC + 2;          // DMA instructions: per code plane, per block
+  static constexpr int kSclOff = 2 * kCodes;                     // K scales in the slot; V scales 1 KB further
+  static constexpr int kSlot = 2 * kCodes + 2048;
+  static constexpr int kQBytes = 8 * D * 2;
+  static constexpr int kMaxThreads = 512;
+  static __device__ __forceinline__ int swz(int row) { return (row >> RSH) & (CPR - 1); }
+  // a chunk = 4 words of 8 codes; each byte widens to one bf16 pair for one packed dot product
+  static __device__ __forceinline__ void qk(const uint4_ kw, float sf, const bf16_t* q, float& sc0, float& sc1) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const bf16x8d qv = __builtin_bit_cast(bf16x8d, *reinterpret_cast<const uint4_*>(q + 8 * i));
+      sc0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(kw[i], sf, 0), DA_PAIR(qv, 0),
+                                            sc0, false);
+      sc1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(kw[i], sf, 1), DA_PAIR(qv, 1),
+                                            sc1, false);
+      sc0 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(kw[i], sf, 2), DA_PAIR(qv, 2),
+                                            sc0, false);
+      sc1 = __builtin_amdgcn_fdot2_f32_bf16(__builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(kw[i], sf, 3), DA_PAIR(qv, 3),
+                                            sc1, false);
+    }
+  }
+  // D = 128: v0 / v1 point at this lane's byte (dims 2l, 2l+1) of keys k, k+1; sa / sb are the keys' group scales
+  static __device__ __forceinline__ void pv2(const E* v0, const E* v1, float sa, float sb, bf16x2d pp, float& c0,
+                                             float& c1) {
+    const uint32_t va = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((uint32_t)*v0, sa, 0));
+    const uint32_t vb = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4((uint32_t)*v1, sb, 0));
+    const uint32_t lo = __builtin_amdgcn_perm(vb, va, 0x05040100u);  // (V[k][2l],   V[k+1][2l])
+    const uint32_t hi = __builtin_amdgcn_perm(vb, va, 0x07060302u);  // (V[k][2l+1], V[k+1][2l+1])
+    c0 = __builtin_amdgcn_fdot2_f32_bf16(pp, __builtin_bit_cast(bf16x2d, lo), c0, false);
+    c1 = __builtin_amdgcn_fdot2_f32_bf16(pp, __builtin_bit_cast(bf16x2d, hi), c1, false);
+  }
+  static __device__ __forceinline__ float qk_scale(const DecodeAttnArgs& p) { return p.scale; }
+  static __device__ __forceinline__ float out_scale(const DecodeAttnArgs&) { return 1.f; }
+  // This step's k: lanes < D/2 hold the pair (x0, x1) = dims (lane, lane + D/2); rotated by kv8_rope_k and rounded
+  // to bf16 (the stored codes are checked exactly), quantised per 32-lane group, widened again for the score.  q =
+  // this lane's code | its right neighbour's << 4, for each half, and the two scale bytes.  Every lane calls.
+  static __device__ __forceinline__ void new_k(float x0, float x1, float c, float sn, float& k0, float& k1,
+                                               uint32_t& q) {
+    float ra, rb;
+    kv8_rope_k(x0, x1, c, sn, ra, rb);
+    const float kr0 = bf2f(f2bf(ra)), kr1 = bf2f(f2bf(rb));
+    const uint32_t b0 = kv4_scale_byte(kv4_group_max<32>(kv4_abs_bits(kr0)));
+    const uint32_t b1 = kv4_scale_byte(kv4_group_max<32>(kv4_abs_bits(kr1)));
+    const uint32_t c0 = kv4_code(kr0, kv4_inv(b0)), c1 = kv4_code(kr1, kv4_inv(b1));
+    k0 = kv4_val(c0, kv4_scale(b0));
+    k1 = kv4_val(c1, kv4_scale(b1));
+    const uint32_t n0 = (uint32_t)__shfl_xor((int)c0, 1, 64), n1 = (uint32_t)__shfl_xor((int)c1, 1, 64);
+    q = (c0 | (n0 << 4)) | ((c1 | (n1 << 4)) << 8) | (b0 << 16) | (b1 << 24);
+  }
+  // kr: the K region of the token's (block, head); even lanes < D/2 write a code byte of each half, the first lane
+  // of a group its two scale bytes
+  static __device__ __forceinline__ void store_k(E* kr, int row, int lane, uint32_t q) {
+    if (lane < D / 2 && (lane & 1) == 0) {
+      kr[row * kRow + (lane >> 1)] = (uint8_t)(q & 0xffu);
+      kr[row * kRow + D / 4 + (lane >> 1)] = (uint8_t)((q >> 8) & 0xffu);
+    }
+    if (lane < D / 2 && (lane & 31) == 0) {
+      kr[kCodes + row * kSclRow + (lane >> 5)] = (uint8_t)((q >> 16) & 0xffu);
+      kr[kCodes + row * kSclRow + D / 64 + (lane >> 5)] = (uint8_t)(q >> 24);
+    }
+  }
+  // This step's v.  D = 128: the lane's dims (2l, 2l + 1) are one byte, a group is 16 lanes; D = 64: lane = dim, a
+  // group is 32 lanes and even lanes hold the byte.  q = code byte | scale byte << 8
+  static __device__ __forceinline__ void new_v(uint32_t vn_pair, float vn_one, float& v0, float& v1, uint32_t& q) {
+    if constexpr (D == 128) {
+      const float a0 = bf2f(vn_pair & 0xffff), a1 = bf2f(vn_pair >> 16);
+      const uint32_t b = kv4_scale_byte(kv4_group_max<16>(max(kv4_abs_bits(a0), kv4_abs_bits(a1))));
+      const uint32_t c0 = kv4_code(a0, kv4_inv(b)), c1 = kv4_code(a1, kv4_inv(b));
+      v0 = kv4_val(c0, kv4_scale(b));
+      v1 = kv4_val(c1, kv4_scale(b));
+      q = c0 | (c1 << 4) | (b << 8);
+    } else {
+      const uint32_t b = kv4_scale_byte(kv4_group_max<32>(kv4_abs_bits(vn_one)));
+      const uint32_t c0 = kv4_code(vn_one, kv4_inv(b));
+      v0 = kv4_val(c0, kv4_scale(b));
+      q = c0 | ((uint32_t)__shfl_xor((int)c0, 1, 64) << 4) | (b << 8);
+    }
+  }
+  static __device__ __forceinline__ void store_v(E* vr, int row, int lane, uint32_t q) {
+    if constexpr (D == 128) {
+      vr[row * kRow + lane] = (uint8_t)(q & 0xffu);
+      if ((lane & 15) == 0) vr[kCodes + row * kSclRow + (lane >> 4)] = (uint8_t)(q >> 8);
+    } else {
+      if ((lane & 1) == 0) vr[row * kRow + (lane >> 1)] = (uint8_t)(q & 0xffu);
+      if ((lane & 31) == 0) vr[kCodes + row * kSclRow + (lane >> 5)] = (uint8_t)(q >> 8);
+    }
+  }
+};
+
+// ----------------------------------------------------------------------------
 // Split decode attention, one (sequence, KV head, split) item: G = Hq/Hkv waves, one query head each (wave w =
 // head hk*G+w).  The 64-token K/V blocks stream global -> LDS by LDS-DMA (buffer_load ... lds) into a two-slot
 // ring: block i+1's DMA is in flight while block i is consumed (counted vmcnt of NI instructions per wave per
@@ -222,7 +391,7 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
                                                  const int split) {
   typedef typename Fmt::E E;
   constexpr int CPR = Fmt::CPR, RPI = Fmt::RPI, EPC = Fmt::EPC, EB = sizeof(E);
-  constexpr int SLOT = 2 * 64 * D;              // elements per ring slot (K then V)
+  constexpr int SLOT = Fmt::kSlot;              // elements per ring slot (K then V)
   E* ring = reinterpret_cast<E*>(dsm);  // [2][K 64xD swizzled | V 64xD linear]
   // q stays bf16 (exact: it is the QKV GEMM's bf16 output) for the packed bf16 dot products; the softmax scale
   // is applied to the f32 score
@@ -257,8 +426,45 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
     return __builtin_amdgcn_readfirstlane(__shfl(my_phys, bi - chunk0, 64));
   };
   // wave w issues instructions j = w + G*t (t < NI) of the block's 2 * 64 * D * EB / 1024 = NI * G
+  // (MXFP4: this wave's share of the block's kNT instructions, NI or NI - 1)
+  int my_ni = NI;
+  if constexpr (Fmt::kMx) my_ni = w < Fmt::kNT ? (Fmt::kNT - w + G - 1) / G : 0;
   auto stage = [&](int slot, int bi) {
     const int phys = phys_of(bi);
+    if constexpr (Fmt::kMx) {
+      // instructions 0 .. kNC-1: K codes, kNC .. 2 kNC-1: V codes, then the K and the V scale plane
+      const long base = ((long)phys * p.Hkv + hk) * Fmt::kRegion;
+      const __amdgpu_buffer_rsrc_t rk =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<E*>(kc + base), (short)0, Fmt::kRegion, 0x00020000);
+      const __amdgpu_buffer_rsrc_t rv =
+          __builtin_amdgcn_make_buffer_rsrc(const_cast<E*>(vc + base), (short)0, Fmt::kRegion, 0x00020000);
+      E* dst = ring + slot * SLOT;
+#pragma unroll
+      for (int t = 0; t < NI; ++t) {
+        const int j = w + G * t;
+        if (j >= Fmt::kNT) break;
+        const bool scl = j >= 2 * Fmt::kNC;
+        const bool isv = scl ? j > 2 * Fmt::kNC : j >= Fmt::kNC;
+        uint32_t off;
+        int at;
+        if (scl) {  // lane = 16-byte chunk of the plane = 512 / D rows
+          const bool in = lane < D / 8 && bi * 64 + lane * (512 / D) < ctx;
+          off = in ? (uint32_t)(Fmt::kCodes + lane * 16) : 0x80000000u;
+          at = Fmt::kSclOff + (isv ? 1024 : 0);
+        } else {
+          const int jj = isv ? j - Fmt::kNC : j;
+          const int row = jj * RPI + lane / CPR;
+          const int pos = lane % CPR;
+          const int ch = isv ? pos : (pos ^ Fmt::swz(row));  // K: source-side XOR swizzle
+          off = (bi * 64 + row < ctx) ? (uint32_t)(row * Fmt::kRow + ch * 16) : 0x80000000u;
+          at = (isv ? Fmt::kCodes : 0) + jj * 1024;
+        }
+        SHAI_DASSERT_DMA(off, Fmt::kRegion, 0x80000000u);
+        SHAI_DASSERT(at + 1024 <= SLOT);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(isv ? rv : rk, (da_lds_void*)(dst + at), 16, off, 0, 0, 0);
+      }
+      return;
+    }
     const long base = ((long)phys * p.Hkv + hk) * 64 * D;
     const __amdgpu_buffer_rsrc_t rk =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<E*>(kc + base), (short)0, 64 * D * EB, 0x00020000);
@@ -363,7 +569,11 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
 #if SHAI_DEBUG
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #else
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");  // block bi landed, bi+1 in flight
+      if (!Fmt::kMx || my_ni == NI) {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");  // block bi landed, bi+1 in flight
+      } else {
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI - 1) : "memory");
+      }
 #endif
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -375,10 +585,29 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
     const int key = bi * 64 + lane;  // lane = key
     // QK^T: one 16-byte K chunk per step, two independent chains
     float sc0 = 0.f, sc1 = 0.f;
+    if constexpr (Fmt::kMx) {
+      // this key's D/32 scale bytes, then one chunk = one scale group per step
+      const E* sKs = sK + Fmt::kSclOff + lane * Fmt::kSclRow;
+      const uint32_t ksc = D == 128 ? *reinterpret_cast<const uint32_t*>(sKs) : *reinterpret_cast<const uint16_t*>(sKs);
+      // the context's last scale chunk can hold never-written bytes for its rows past the context: zero the V ones
+      if (bi * 64 + 64 > ctx) {
+        if (key >= ctx) {
+          E* sVs = const_cast<E*>(sK) + Fmt::kSclOff + 1024 + lane * Fmt::kSclRow;
+          if constexpr (D == 128) *reinterpret_cast<uint32_t*>(sVs) = 0u;
+          else *reinterpret_cast<uint16_t*>(sVs) = 0;
+        }
+      }
 #pragma unroll
-    for (int ch = 0; ch < CPR; ++ch) {
-      const uint4_ kw = *reinterpret_cast<const uint4_*>(sK + lane * D + (ch ^ Fmt::swz(lane)) * EPC);
-      Fmt::qk(kw, sQb + w * D + ch * EPC, sc0, sc1);
+      for (int ch = 0; ch < CPR; ++ch) {
+        const uint4_ kw = *reinterpret_cast<const uint4_*>(sK + lane * Fmt::kRow + (ch ^ Fmt::swz(lane)) * 16);
+        Fmt::qk(kw, kv4_scale((ksc >> (8 * ch)) & 0xffu), sQb + w * D + ch * EPC, sc0, sc1);
+      }
+    } else {
+#pragma unroll
+      for (int ch = 0; ch < CPR; ++ch) {
+        const uint4_ kw = *reinterpret_cast<const uint4_*>(sK + lane * D + (ch ^ Fmt::swz(lane)) * EPC);
+        Fmt::qk(kw, sQb + w * D + ch * EPC, sc0, sc1);
+      }
     }
     float sc = (sc0 + sc1) * sl2;
     if (key >= ctx) sc = -INFINITY;
@@ -403,8 +632,22 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
       for (int k = 0; k < 64; k += 8) {
         // P[k .. k+7] as 4 bf16 pairs
         const bf16x8d pk = __builtin_bit_cast(bf16x8d, *reinterpret_cast<const uint4_*>(sPb + w * 64 + k));
+        uint4_ vs0 = {0u, 0u, 0u, 0u}, vs1 = {0u, 0u, 0u, 0u};  // MXFP4: the 8 keys' scale words (same for every lane)
+        if constexpr (Fmt::kMx) {
+          vs0 = *reinterpret_cast<const uint4_*>(sK + Fmt::kSclOff + 1024 + k * 4);
+          vs1 = *reinterpret_cast<const uint4_*>(sK + Fmt::kSclOff + 1024 + k * 4 + 16);
+        }
         auto pvf = [&](int u, bf16x2d pp, float& c0, float& c1) {
-          Fmt::pv2(sV + (k + 2 * u) * D + 2 * lane, sV + (k + 2 * u + 1) * D + 2 * lane, pp, c0, c1);
+          if constexpr (Fmt::kMx) {
+            // this lane's dims 2l, 2l + 1 sit in group l / 16: byte l >> 4 of a key's scale word
+            const uint4_ vs = u < 2 ? vs0 : vs1;
+            const int sh = (lane >> 4) * 8;
+            const E* vcod = sK + Fmt::kCodes + (k + 2 * u) * Fmt::kRow + lane;
+            Fmt::pv2(vcod, vcod + Fmt::kRow, kv4_scale((vs[(2 * u) & 3] >> sh) & 0xffu),
+                     kv4_scale((vs[(2 * u + 1) & 3] >> sh) & 0xffu), pp, c0, c1);
+          } else {
+            Fmt::pv2(sV + (k + 2 * u) * D + 2 * lane, sV + (k + 2 * u + 1) * D + 2 * lane, pp, c0, c1);
+          }
         };
         pvf(0, DA_PAIR(pk, 0), o0, o1);
         pvf(1, DA_PAIR(pk, 1), a0, a1);
@@ -422,7 +665,15 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
       for (int k = 0; k < 64; k += 4) {
         const float4_ pk = *reinterpret_cast<const float4_*>(sP + w * 64 + k);
 #pragma unroll
-        for (int u = 0; u < 4; ++u) o0 += pk[u] * Fmt::v_f32(sV[(k + u) * D + lane]);
+        for (int u = 0; u < 4; ++u) {
+          if constexpr (Fmt::kMx) {  // lane = dim: nibble lane & 1 of byte lane / 2, scale byte lane / 32 of the key
+            const uint32_t cb = sK[Fmt::kCodes + (k + u) * Fmt::kRow + (lane >> 1)];
+            const uint32_t sb = sK[Fmt::kSclOff + 1024 + (k + u) * Fmt::kSclRow + (lane >> 5)];
+            o0 += pk[u] * kv4_val(cb >> (4 * (lane & 1)), kv4_scale(sb));
+          } else {
+            o0 += pk[u] * Fmt::v_f32(sV[(k + u) * D + lane]);
+          }
+        }
       }
     }
     __builtin_amdgcn_s_barrier();  // every wave is done with this slot before it is refilled (block bi+2)
@@ -433,7 +684,10 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
     const int slot_new = p.slots[b];
     float k0 = 0.f, k1 = 0.f, part_s = 0.f;
     uint32_t kq = 0u, vq = 0u;
-    if (lane < D / 2) {
+    if constexpr (Fmt::kMx) {  // the group amax is a cross-lane max: every lane calls (lanes >= D/2 hold zeros)
+      Fmt::new_k(kn0, kn1, kc0, ks0, k0, k1, kq);
+      if (lane < D / 2) part_s = k0 * bf2f(sQb[w * D + lane]) + k1 * bf2f(sQb[w * D + lane + D / 2]);
+    } else if (lane < D / 2) {
       Fmt::new_k(p, kn0, kn1, kc0, ks0, k0, k1, kq);
       part_s = k0 * bf2f(sQb[w * D + lane]) + k1 * bf2f(sQb[w * D + lane + D / 2]);
     }
@@ -445,13 +699,20 @@ __device__ __forceinline__ void decode_attn_item(const DecodeAttnArgs& p, char* 
     l_run = l_run * alpha + e;
     m_run = m_new;
     float v0 = 0.f, v1 = 0.f;
-    Fmt::new_v(p, vn_pair, vn_one, v0, v1, vq);
+    if constexpr (Fmt::kMx) Fmt::new_v(vn_pair, vn_one, v0, v1, vq);
+    else Fmt::new_v(p, vn_pair, vn_one, v0, v1, vq);
     o0 = o0 * alpha + e * v0;
     if constexpr (D == 128) o1 = o1 * alpha + e * v1;
     if (w == 0) {
-      const long dst = (((long)(slot_new >> 6) * p.Hkv + hk) * 64 + (slot_new & 63)) * D;
-      if (lane < D / 2) Fmt::store_k(const_cast<E*>(kc) + dst + lane, k0, k1, kq);
-      Fmt::store_v(const_cast<E*>(vc) + dst + (D == 128 ? 2 * lane : lane), vn_pair, vn_one, vq);
+      if constexpr (Fmt::kMx) {
+        const long reg = ((long)(slot_new >> 6) * p.Hkv + hk) * Fmt::kRegion;
+        Fmt::store_k(const_cast<E*>(kc) + reg, slot_new & 63, lane, kq);
+        Fmt::store_v(const_cast<E*>(vc) + reg, slot_new & 63, lane, vq);
+      } else {
+        const long dst = (((long)(slot_new >> 6) * p.Hkv + hk) * 64 + (slot_new & 63)) * D;
+        if (lane < D / 2) Fmt::store_k(const_cast<E*>(kc) + dst + lane, k0, k1, kq);
+        Fmt::store_v(const_cast<E*>(vc) + dst + (D == 128 ? 2 * lane : lane), vn_pair, vn_one, vq);
+      }
     }
   }
   if (nsp == 1) {  // one split: normalise (out_scale folded in) and write the output here (the combine skips this row)

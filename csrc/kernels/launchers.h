@@ -368,6 +368,8 @@ struct DecodeAttnArgs {
   float scale;
   bool kv_fp8;              // the caches hold fp8 codes (see k_scale below): split kernel only.  (In the padding
                             // behind scale: the kernels' argument layout is what it was without the field)
+  bool kv_fp4;              // the caches hold MXFP4 regions (decode_common.h KvFp4: per (block, KV head) 64 * D/2 code
+                            // bytes, then 64 * D/32 e8m0 scale bytes; no scalar scales): split kernel only
   // fused decode step (knew != nullptr): q is un-roped; this step's k / v rows ([B, Hkv, D] at row stride
   // new_bs) are roped / taken from here, written into the cache at slots[b] (-1: padding row) and attended
   // from registers; ctx_lens count the new token, the cache holds ctx_lens - 1 of them
@@ -401,6 +403,18 @@ void launch_rope_qkv_cache_f8(bf16_t* qkv, long ld, const int* pos, const float*
 void launch_kv_dequant_blocks(const uint8_t* k_cache, const uint8_t* v_cache, const int* phys, int n,
                               long block_elems, bf16_t* k_out, bf16_t* v_out, float k_scale, float v_scale,
                               hipStream_t s);
+// MXFP4 KV cache (attention_kv4.hip): caches are bytes [blocks, Hkv, 64 * (D/2 + D/32)], the region layout of
+// decode_common.h's KvFp4.  The split decode kernel's MXFP4 instantiations (launch_decode_attn routes kv_fp4 here
+// with its grid), the writers (codes and scales bit-equal to ops/reference.py quantize_kv_mxfp4) and the exact
+// block widener into the bf16 scratch [n, Hkv, 64, D]
+void launch_decode_split_kv4(const DecodeAttnArgs& a, unsigned grid, hipStream_t s);
+void launch_kv_write_f4(const bf16_t* k, const bf16_t* v, uint8_t* k_cache, uint8_t* v_cache, const int* slot_mapping,
+                        int T, int Hkv, int D, long k_ts, long v_ts, hipStream_t s);
+void launch_rope_qkv_cache_f4(bf16_t* qkv, long ld, const int* pos, const float* cos, const float* sin,
+                              uint8_t* k_cache, uint8_t* v_cache, const int* slots, int T, int H, int Hkv, int D,
+                              hipStream_t s);
+void launch_kv_dequant_blocks_f4(const uint8_t* k_cache, const uint8_t* v_cache, const int* phys, int n, int Hkv,
+                                 int D, bf16_t* k_out, bf16_t* v_out, hipStream_t s);
 // short-context decode routing (D 128, GQA 4, one split -> the wave-per-block kernel); SHAI_DECODE_WB=0 / mode 0: split kernel
 int decode_wb_mode();
 int set_decode_wb(int mode);   // -1 keeps the mode; returns the previous one

@@ -645,19 +645,22 @@ class _Inflight:
 
 
 KV_CACHE_DTYPES = {"auto": torch.bfloat16, "bf16": torch.bfloat16, "bfloat16": torch.bfloat16,
-                   "fp8": torch.float8_e4m3fn, "fp8_e4m3": torch.float8_e4m3fn}
+                   "fp8": torch.float8_e4m3fn, "fp8_e4m3": torch.float8_e4m3fn,
+                   "mxfp4": torch.uint8, "fp4": torch.uint8}
 
 
 def resolve_kv_cache_dtype(kv_cache_dtype: Optional[str]):
     """vLLM-style ``kv_cache_dtype``: None reads ``SHAI_KV_CACHE_DTYPE`` (unset: auto); auto / bf16 keep the bf16
-    cache, fp8 / fp8_e4m3 select the OCP e4m3fn cache.  Returns (canonical name, torch dtype)."""
+    cache, fp8 / fp8_e4m3 select the OCP e4m3fn cache, mxfp4 / fp4 the OCP MXFP4 cache (e2m1 codes + an e8m0 scale
+    per 32 elements, stored as uint8).  Returns (canonical name, torch dtype)."""
     name = kv_cache_dtype if kv_cache_dtype is not None else os.environ.get("SHAI_KV_CACHE_DTYPE")
     name = "auto" if name is None or str(name).strip() == "" else str(name).strip().lower()
     if name not in KV_CACHE_DTYPES:
         raise ValueError(f"kv_cache_dtype={kv_cache_dtype if kv_cache_dtype is not None else name!r}: supported: "
-                         "auto, bf16 (bfloat16 cache) or fp8, fp8_e4m3 (OCP e4m3fn cache with scalar k/v scales)")
+                         "auto, bf16 (bfloat16 cache), fp8, fp8_e4m3 (OCP e4m3fn cache with scalar k/v scales) or "
+                         "mxfp4, fp4 (OCP MXFP4 cache: e2m1 codes with an e8m0 scale per 32 elements)")
     dt = KV_CACHE_DTYPES[name]
-    return ("fp8" if dt == torch.float8_e4m3fn else "auto"), dt
+    return ("fp8" if dt == torch.float8_e4m3fn else "mxfp4" if dt == torch.uint8 else "auto"), dt
 
 
 class LLMEngine:
@@ -675,15 +678,28 @@ class LLMEngine:
         from ..runtime import BlockManager
         self.kv_cache_dtype, self.kv_dtype = resolve_kv_cache_dtype(kv_cache_dtype)
         self.kv_fp8 = self.kv_dtype == torch.float8_e4m3fn
+        # MXFP4 cache: group scales inside the cache (no scalar scales), decode reads the codes, every prefill step
+        # takes the "widen" route (there is no native 4-bit prefill kernel yet)
+        self.kv_fp4 = self.kv_dtype == torch.uint8
+        if self.kv_fp4:
+            if kv_prefill is not None and ops.resolve_kv_prefill(kv_prefill) == "native":
+                raise NotImplementedError("kv_prefill='native' with kv_cache_dtype=mxfp4: the native 4-bit paged "
+                                          "prefill kernel is a follow-up; the mxfp4 cache takes the widen route")
+            if float(k_scale) != 1.0 or float(v_scale) != 1.0:
+                raise ValueError("kv_cache_dtype=mxfp4 has group scales only: k_scale / v_scale must be 1.0, got "
+                                 f"{k_scale}, {v_scale}")
+            if self.speculative is not None:
+                raise NotImplementedError("speculative decoding is not supported yet with kv_cache_dtype=mxfp4: the "
+                                          "verify step needs the native 4-bit prefill kernel, a follow-up")
         # fp8 cache, prefill / mixed steps: "native" (the paged kernel reads the codes; no scratch) or "widen"
         # (the bf16 scratch + rounds below); None reads SHAI_KV8_PREFILL (unset: widen).  Unused with a bf16 cache.
-        self.kv_prefill = ops.resolve_kv_prefill(kv_prefill)
+        self.kv_prefill = "widen" if self.kv_fp4 else ops.resolve_kv_prefill(kv_prefill)
         if self.kv_fp8 and self.kv_prefill == "native" and kv_scratch_blocks is not None:
             raise ValueError("kv_prefill='native' allocates no dequantisation scratch: kv_scratch_blocks="
                              f"{kv_scratch_blocks} has no meaning with it")
         self.mcfg = cfg if isinstance(cfg, MllamaConfig) else None
-        if self.kv_fp8 and self.mcfg is not None:
-            raise NotImplementedError("kv_cache_dtype=fp8 is not supported yet for multimodal (mllama) models: the "
+        if (self.kv_fp8 or self.kv_fp4) and self.mcfg is not None:
+            raise NotImplementedError(f"kv_cache_dtype={self.kv_cache_dtype} is not supported yet for multimodal (mllama) models: the "
                                       "image cross-attention K/V path is bf16 only")
         if self.speculative is not None and self.mcfg is not None:
             raise NotImplementedError("speculative decoding is not supported yet for multimodal (mllama) models: the "
@@ -750,7 +766,7 @@ class LLMEngine:
         scratch_bytes = 0
         if self.kv_fp8:
             self.set_kv_scales(self.k_scales, self.v_scales)
-        if self.kv_fp8 and self.kv_prefill == "widen":
+        if (self.kv_fp8 or self.kv_fp4) and self.kv_prefill == "widen":
             want = kv_scratch_blocks if kv_scratch_blocks is not None else max(
                 self.max_blocks + 1, (prefill_token_budget + KV_BLOCK - 1) // KV_BLOCK + max_num_seqs)
             self.kv_scratch_blocks = max(int(want), self.max_blocks + 1)
@@ -844,7 +860,7 @@ class LLMEngine:
     def _attach_kv_rounds(self, batch: Batch, bt, lens, qlens, qstart, S: int) -> None:
         """fp8 cache, "widen" route: plan this prefill step's dequant + attention rounds from the host block lists
         (no device sync) and hand the scratch to the model.  The "native" route plans nothing."""
-        if not self.kv_fp8:
+        if not (self.kv_fp8 or self.kv_fp4):
             return
         batch.kv_prefill = self.kv_prefill
         if self.kv_prefill == "native":

@@ -405,13 +405,28 @@ class LlamaForCausalLM(nn.Module):
 
 
 def allocate_kv_cache(cfg: LlamaConfig, kv_heads_local: int, num_blocks: int, device, dtype=torch.bfloat16):
-    """One contiguous allocation [L, 2, blocks, Hkv, 64, hd]; returns list of (k, v) views per layer."""
-    buf = torch.empty(cfg.num_hidden_layers, 2, num_blocks, kv_heads_local, KV_BLOCK, cfg.head_dim, dtype=dtype,
+    """One contiguous allocation [L, 2, blocks, Hkv, 64, hd]; returns list of (k, v) views per layer.  uint8 is the
+    MXFP4 cache: hd / 2 + hd / 32 bytes per row (per (block, head) a code plane, then a scale plane)."""
+    width = kv_row_bytes(cfg.head_dim, dtype) // torch.empty((), dtype=dtype).element_size()
+    if dtype == torch.uint8:   # every region starts out as valid codes and scales (zeros), never a NaN scale byte
+        buf = torch.zeros(cfg.num_hidden_layers, 2, num_blocks, kv_heads_local, KV_BLOCK, width, dtype=dtype,
+                          device=device)
+        return buf, [(buf[i, 0], buf[i, 1]) for i in range(cfg.num_hidden_layers)]
+    buf = torch.empty(cfg.num_hidden_layers, 2, num_blocks, kv_heads_local, KV_BLOCK, width, dtype=dtype,
                       device=device)
     return buf, [(buf[i, 0], buf[i, 1]) for i in range(cfg.num_hidden_layers)]
 
 
 def kv_bytes_per_block(cfg: LlamaConfig, kv_heads_local: int, dtype=torch.bfloat16) -> int:
-    """Bytes of one 64-token block across all layers (K and V) at the cache dtype (bf16: 2 bytes, fp8: 1)."""
-    esize = torch.empty((), dtype=dtype).element_size()
-    return cfg.num_hidden_layers * 2 * kv_heads_local * KV_BLOCK * cfg.head_dim * esize
+    """Bytes of one 64-token block across all layers (K and V) at the cache dtype (bf16: 2 bytes per element, fp8:
+    1, MXFP4 (uint8): 1/2 + 1/32)."""
+    return cfg.num_hidden_layers * 2 * kv_heads_local * KV_BLOCK * kv_row_bytes(cfg.head_dim, dtype)
+
+
+def kv_row_bytes(head_dim: int, dtype=torch.bfloat16) -> int:
+    """Cache bytes of one token of one KV head, K or V."""
+    if dtype == torch.uint8:
+        if head_dim not in (64, 128):
+            raise ValueError(f"kv_cache_dtype=mxfp4 needs head_dim 64 or 128, got {head_dim}")
+        return head_dim // 2 + head_dim // 32
+    return head_dim * torch.empty((), dtype=dtype).element_size()

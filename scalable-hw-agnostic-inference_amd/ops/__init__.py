@@ -27,7 +27,7 @@ __all__ = [
     "paged_attention", "decode_attention", "kv_write", "rope", "rope_pairs", "gated_act", "bias_act", "sched_step",
     "softmax_", "embedding", "token_feedback", "decode_attention_rope", "decode_attention_rope_qkv", "gemm_partials", "quantize_fp8_rows", "dequant_fp8", "quantize_mxfp4", "dequant_mxfp4", "mxfp4_pack", "mxfp4_unpack", "is_mxfp4", "NF4_TABLE", "quantize_nf4", "dequant_nf4", "nf4_pack", "nf4_unpack", "is_nf4", "quant_rows_fp8", "gemm_f8", "pack_conv_weight", "pack_up2_phase_weight", "linear_wslices", "unpack_conv_weight", "act_id", "ACT_NONE", "ACT_SILU", "ACT_GELU",
     "ACT_GELU_TANH", "ACT_QUICK_GELU", "ACT_RELU", "decode_splits", "set_decode_wb",
-    "paged_attention_varlen", "rope_qkv_cache", "quantize_kv_fp8", "dequant_kv_fp8", "kv_dequant_blocks",
+    "paged_attention_varlen", "rope_qkv_cache", "quantize_kv_fp8", "dequant_kv_fp8", "quantize_kv_mxfp4", "dequant_kv_mxfp4", "kv_dequant_blocks",
     "plan_kv_scratch", "build_kv_rounds", "KVRound", "FP8_KV_DTYPE", "resolve_kv_prefill", "KV_PREFILL_ROUTES",
     "sample_penalized", "penalty_state_init", "token_logprobs", "LOGPROBS_MAX",
     "sample_constrained", "constraint_state_init",
@@ -703,6 +703,24 @@ def _kv8(k_cache, v_cache) -> bool:
     return k_cache.dtype == FP8_KV_DTYPE
 
 
+def _kv4(k_cache, v_cache) -> bool:
+    """True for an MXFP4 cache pair (uint8 [blocks, Hkv, 64, D/2 + D/32], ``ref.mxfp4_kv_planes``); a mixed pair is
+    an error on every path."""
+    ref._check_kv_pair(k_cache, v_cache)
+    return ref.is_mxfp4_kv(k_cache)
+
+
+def quantize_kv_mxfp4(x: torch.Tensor):
+    """The MXFP4 KV-cache rule on rows x [..., D]: (codes uint8 [..., D / 2], e8m0 scale bytes uint8 [..., D / 32]),
+    ``quantize_mxfp4``'s rule per group of 32."""
+    return ref.quantize_kv_mxfp4(x)
+
+
+def dequant_kv_mxfp4(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """code * 2^(scale byte - 127) -> [..., D] (exact in bf16)."""
+    return ref.dequant_kv_mxfp4(codes, scales, dtype)
+
+
 def quantize_kv_fp8(x: torch.Tensor, scale: float = 1.0) -> torch.Tensor:
     """The fp8 KV-cache quantisation rule: RNE e4m3fn of clamp(float(x) * (1 / scale), -448, 448)."""
     return ref.quantize_kv_fp8(x, scale)
@@ -715,11 +733,14 @@ def dequant_kv_fp8(c: torch.Tensor, scale: float = 1.0, dtype=torch.bfloat16) ->
 
 def kv_dequant_blocks(k_cache, v_cache, phys, k_out, v_out, k_scale: float = 1.0, v_scale: float = 1.0):
     """Widen the fp8 cache blocks ``phys`` [n] into blocks 0 .. n-1 of the bf16 scratch caches ``k_out`` / ``v_out``
-    [capacity, Hkv, 64, D] (value = float(code) * scale).  One launch for K and V."""
+    [capacity, Hkv, 64, D] (value = float(code) * scale).  One launch for K and V.  An MXFP4 cache widens exactly
+    (code * group scale; ``k_scale`` / ``v_scale`` must be 1)."""
+    if _kv4(k_cache, v_cache):
+        ref._check_mxfp4_scales(k_scale, v_scale)
     if not _gpu(k_cache):
         return ref.kv_dequant_blocks(k_cache, v_cache, phys, k_out, v_out, k_scale, v_scale)
-    if not _kv8(k_cache, v_cache):
-        raise ValueError(f"kv_dequant_blocks needs float8_e4m3fn caches, got {k_cache.dtype}")
+    if not (_kv8(k_cache, v_cache) or _kv4(k_cache, v_cache)):
+        raise ValueError(f"kv_dequant_blocks needs float8_e4m3fn or mxfp4 (uint8) caches, got {k_cache.dtype}")
     _K().kv_dequant_blocks(k_cache, v_cache, _i32(phys), k_out, v_out, float(k_scale), float(v_scale))
 
 
@@ -792,6 +813,16 @@ def build_kv_rounds(block_table, kv_lens, q_lens, q_start, capacity: int, device
 KV_PREFILL_ROUTES = ("widen", "native")
 
 
+def _kv4_prefill(k_cache, v_cache, kv_prefill, k_scale, v_scale) -> None:
+    """An MXFP4 cache has the widen route only, and no scalar scales."""
+    if not _kv4(k_cache, v_cache):
+        return
+    ref._check_mxfp4_scales(k_scale, v_scale)
+    if kv_prefill is not None and resolve_kv_prefill(kv_prefill) == "native":
+        raise NotImplementedError("kv_prefill='native' over an mxfp4 KV cache: the native 4-bit paged prefill "
+                                  "kernel is a follow-up; use kv_prefill='widen'")
+
+
 def resolve_kv_prefill(kv_prefill: Optional[str] = None) -> str:
     """Route of the prefill attention over an fp8 cache: ``native`` reads the codes in the paged flash kernel (one
     launch: no scratch, no rounds, no host read of device metadata); ``widen`` copies the blocks a step needs into
@@ -817,7 +848,7 @@ def _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q
                                  max(need, 1), q.device, max_q)
     if scratch is None:
         cap = max(max(r.n_blocks for r in rounds), 1)
-        shape = (cap,) + tuple(k_cache.shape[1:])
+        shape = (cap,) + tuple(k_cache.shape[1:3]) + (ref.kv_head_dim(k_cache),)
         scratch = (torch.empty(shape, dtype=q.dtype, device=q.device), torch.empty(shape, dtype=q.dtype,
                                                                                    device=q.device))
     ks, vs = scratch
@@ -849,6 +880,7 @@ def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=Non
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     native = _kv8(k_cache, v_cache) and resolve_kv_prefill(kv_prefill) == "native"
+    _kv4_prefill(k_cache, v_cache, kv_prefill, k_scale, v_scale)
     if not _gpu(q):
         return ref.paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale, causal, k_scale, v_scale)
     if native:
@@ -856,7 +888,7 @@ def paged_attention(q, k_cache, v_cache, block_table, kv_lens, q_lens, scale=Non
         _K().flash_attn(q, k_cache, v_cache, o, float(scale), bool(causal), 0, _i32(kv_lens), _i32(q_lens), None,
                         _i32(block_table), float(k_scale), float(v_scale))
         return o
-    if _kv8(k_cache, v_cache):
+    if _kv8(k_cache, v_cache) or _kv4(k_cache, v_cache):
         return _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, None, q.shape[1], scale, causal,
                           k_scale, v_scale, scratch, rounds)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
@@ -876,6 +908,7 @@ def paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_
     D = q.shape[-1]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     native = _kv8(k_cache, v_cache) and resolve_kv_prefill(kv_prefill) == "native"
+    _kv4_prefill(k_cache, v_cache, kv_prefill, k_scale, v_scale)
     if not _gpu(q):
         return ref.paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, scale, causal,
                                           k_scale, v_scale)
@@ -890,7 +923,7 @@ def paged_attention_varlen(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_
                                        ql[first:first + n], qs[first:first + n], int(mq), float(scale), bool(causal),
                                        float(k_scale), float(v_scale))
         return o
-    if _kv8(k_cache, v_cache):
+    if _kv8(k_cache, v_cache) or _kv4(k_cache, v_cache):
         return _paged_kv8(q, k_cache, v_cache, block_table, kv_lens, q_lens, q_start, max_q, scale, causal, k_scale,
                           v_scale, scratch, rounds)
     o = torch.empty(q.shape, dtype=q.dtype, device=q.device)
@@ -922,7 +955,11 @@ def decode_splits(batch: int, hkv: int, max_ctx: int) -> int:
 
 
 def _kv8_kw(k_cache, v_cache, k_scale, v_scale) -> dict:
-    """Extra kernel arguments of an fp8 cache (none for bf16: those calls stay exactly as they were)."""
+    """Extra kernel arguments of an fp8 cache (none for bf16: those calls stay exactly as they were; none for an
+    MXFP4 cache, whose scalar scales must be 1)."""
+    if _kv4(k_cache, v_cache):
+        ref._check_mxfp4_scales(k_scale, v_scale)
+        return {}
     return {"k_scale": float(k_scale), "v_scale": float(v_scale)} if _kv8(k_cache, v_cache) else {}
 
 
@@ -951,7 +988,7 @@ SPEC_MAX_T = 8   # query tokens per sequence the verify kernel takes (1 + up to 
 def spec_attention_native(q, k_cache, v_cache) -> bool:
     """Whether :func:`spec_attention` runs csrc/kernels/attention_spec.hip for these operands (GPU, bf16 cache,
     D 64 / 128, T <= 8, Hq / Hkv in {1, 2, 4, 8}); everything else takes the padded paged prefill kernel."""
-    if not _gpu(q) or _kv8(k_cache, v_cache) or os.environ.get("SHAI_SPEC_ATTN", "1") == "0":
+    if not _gpu(q) or _kv8(k_cache, v_cache) or _kv4(k_cache, v_cache) or os.environ.get("SHAI_SPEC_ATTN", "1") == "0":
         return False
     _, T, Hq, D = q.shape
     Hkv = k_cache.shape[1]
@@ -994,7 +1031,7 @@ def decode_attention_rope(qkv, k_cache, v_cache, block_table, ctx_lens, position
     """One fused decode step on the packed QKV rows qkv [B, (h + 2 hk) D]: NeoX RoPE on q / k, this step's k / v
     written into the paged caches at ``slots`` (-1: padding row), attention over the cached context plus the
     new token (``ctx_lens`` count it).  Equivalent to rope_qkv_cache + decode_attention.  Returns [B, h D]."""
-    D = k_cache.shape[-1]
+    D = ref.kv_head_dim(k_cache)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     B = qkv.shape[0]
     if not _gpu(qkv):
@@ -1030,7 +1067,7 @@ def decode_attention_rope_qkv(x, w_qkv, rms_eps: float, k_cache, v_cache, block_
         return decode_attention_rope(linear(x, w_qkv, rms_eps=rms_eps), k_cache, v_cache, block_table, ctx_lens,
                                      positions, cos, sin, slots, h, hk, scale, num_splits, out=out, k_scale=k_scale,
                                      v_scale=v_scale)
-    D = k_cache.shape[-1]
+    D = ref.kv_head_dim(k_cache)
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     B, K = x.shape
     N = w_qkv.shape[0]
@@ -1069,7 +1106,7 @@ def rope_qkv_cache(qkv, positions, cos, sin, k_cache, v_cache, slots, heads: int
     """Packed QKV rows [T, (H + 2Hkv) * D]: NeoX RoPE on q in place, rotated k and v written to the paged
     caches [blocks, Hkv, 64, D] at ``slots`` (-1 = skip).  One fused kernel on the GPU."""
     T = qkv.shape[0]
-    D = k_cache.shape[-1]
+    D = ref.kv_head_dim(k_cache)
     if not _gpu(qkv):
         q = qkv[:, : heads * D].view(T, heads, D)
         k = qkv[:, heads * D:(heads + kv_heads) * D].view(T, kv_heads, D).clone()   # as the kernel: k in qkv stays

@@ -192,6 +192,12 @@ def quantize_mxfp4(w: torch.Tensor):
     """OCP MX quantisation of w [N, K] (K % 32 == 0) along K: per group of 32, e = floor(log2(amax)) - 2 clamped so
     that 0.5 * 2^e is a normal bf16, elements / 2^e clamped to +-6 and rounded to the nearest e2m1 value, ties to
     the even mantissa.  A dequantised weight code * 2^e is exact in bf16.  Returns ``mxfp4_pack``'s pair."""
+    return mxfp4_pack(*mxfp4_quantize_rows(w))
+
+
+def mxfp4_quantize_rows(w: torch.Tensor):
+    """The rule of ``quantize_mxfp4`` in the logical layout: (codes uint8 [N, K / 2], scale bytes uint8 [N, K / 32]).
+    The one quantiser of the weight rows and of the MXFP4 KV cache (``quantize_kv_mxfp4``)."""
     assert w.dim() == 2 and w.shape[1] % MXFP4_GROUP == 0 and w.shape[1] > 0, "quantize_mxfp4: w must be [N, K], K % 32 == 0"
     N, K = w.shape
     wf = w.float().reshape(N, K // MXFP4_GROUP, MXFP4_GROUP)
@@ -207,17 +213,21 @@ def quantize_mxfp4(w: torch.Tensor):
     code = code | (((v < 0) & (code > 0)).to(torch.uint8) << 3)
     code = code.reshape(N, K)
     packed = code[:, 0::2] | (code[:, 1::2] << 4)
-    return mxfp4_pack(packed, (e + 127).to(torch.uint8))
+    return packed, (e + 127).to(torch.uint8)
 
 
 def dequant_mxfp4(wq: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
     """Table decode of ``quantize_mxfp4``'s pair -> [N, K] (exact in bf16 / fp32)."""
-    codes, sb = mxfp4_unpack(wq, scales)
+    return mxfp4_dequant_rows(*mxfp4_unpack(wq, scales), dtype)
+
+
+def mxfp4_dequant_rows(codes: torch.Tensor, sb: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """Table decode in the logical layout: codes uint8 [N, K / 2], scale bytes uint8 [N, K / 32] -> [N, K]."""
     N, K2 = codes.shape
     table = torch.tensor(MXFP4_VALUES + tuple(-x for x in MXFP4_VALUES), dtype=torch.float32, device=codes.device)
     vals = torch.stack([table[(codes & 15).long()], table[(codes >> 4).long()]], dim=-1).reshape(N, K2 * 2)
     e = sb.to(torch.int32) - 127
-    out = torch.ldexp(vals.view(N, -1, MXFP4_GROUP), e[..., None]).reshape(N, K2 * 2)
+    out = torch.ldexp(vals.view(N, K2 * 2 // MXFP4_GROUP, MXFP4_GROUP), e[..., None]).reshape(N, K2 * 2)
     return out.to(dtype)
 
 
@@ -482,25 +492,86 @@ def is_fp8_kv(cache) -> bool:
     return cache.dtype == FP8_KV_DTYPE
 
 
+# ---- MXFP4 KV cache: a K / V row (one token, one KV head, D elements: the value the bf16 cache would have stored)
+# is quantised by ``mxfp4_quantize_rows`` -- the weight rows' rule, groups of 32 consecutive elements.  The cache is
+# uint8 [blocks, H, 64, D/2 + D/32]; per (block, head) the 64 * (D/2 + D/32) bytes are one region: the code plane
+# (64 rows of D/2 bytes, even element in the low nibble), then the scale plane (64 rows of D/32 e8m0 bytes).  The
+# last two dims only spell the region's size.  No scalar k / v scales.
+MXFP4_KV_DTYPE = torch.uint8
+
+
+def is_mxfp4_kv(cache) -> bool:
+    return cache.dtype == MXFP4_KV_DTYPE
+
+
+def mxfp4_kv_head_dim(cache) -> int:
+    """D of an MXFP4 cache tensor (last dim D/2 + D/32)."""
+    return cache.shape[-1] * 32 // 17
+
+
+def kv_head_dim(cache) -> int:
+    return mxfp4_kv_head_dim(cache) if is_mxfp4_kv(cache) else cache.shape[-1]
+
+
+def quantize_kv_mxfp4(x):
+    """The MXFP4 KV-cache quantisation rule (the oracle every writer is tested against): x [..., D] ->
+    (codes uint8 [..., D / 2], scale bytes uint8 [..., D / 32]) by ``mxfp4_quantize_rows`` on the rows."""
+    D = x.shape[-1]
+    codes, sb = mxfp4_quantize_rows(x.reshape(-1, D))
+    return codes.reshape(*x.shape[:-1], D // 2), sb.reshape(*x.shape[:-1], D // MXFP4_GROUP)
+
+
+def dequant_kv_mxfp4(codes, sb, dtype=torch.float32):
+    """value = code * 2^(scale byte - 127): exact in bf16 and fp32."""
+    D = codes.shape[-1] * 2
+    out = mxfp4_dequant_rows(codes.reshape(-1, D // 2), sb.reshape(-1, D // MXFP4_GROUP), dtype)
+    return out.reshape(*codes.shape[:-1], D)
+
+
+def mxfp4_kv_planes(cache):
+    """Views of an MXFP4 cache [..., 64, D/2 + D/32]: (codes [..., 64, D/2], scale bytes [..., 64, D/32])."""
+    D = mxfp4_kv_head_dim(cache)
+    flat = cache.reshape(*cache.shape[:-2], 64 * cache.shape[-1])
+    assert flat.data_ptr() == cache.data_ptr(), "an MXFP4 cache's regions must be contiguous"
+    return (flat[..., :32 * D].unflatten(-1, (64, D // 2)), flat[..., 32 * D:].unflatten(-1, (64, D // MXFP4_GROUP)))
+
+
+def dequant_kv_mxfp4_blocks(blocks, dtype=torch.float32):
+    """MXFP4 cache blocks [..., 64, D/2 + D/32] -> values [..., 64, D]."""
+    return dequant_kv_mxfp4(*mxfp4_kv_planes(blocks), dtype)
+
+
 def _check_kv_pair(k_cache, v_cache):
-    if is_fp8_kv(k_cache) != is_fp8_kv(v_cache):
+    if k_cache.dtype != v_cache.dtype and (is_fp8_kv(k_cache) or is_fp8_kv(v_cache) or is_mxfp4_kv(k_cache)
+                                           or is_mxfp4_kv(v_cache)):
         raise ValueError(f"k_cache / v_cache dtypes differ ({k_cache.dtype} vs {v_cache.dtype})")
 
 
+def _check_mxfp4_scales(k_scale, v_scale):
+    if float(k_scale) != 1.0 or float(v_scale) != 1.0:
+        raise ValueError("an mxfp4 KV cache has group scales only: k_scale / v_scale must be 1.0")
+
+
 def gather_paged(cache, block_table, length, scale=1.0):
-    """cache [blocks, H, 64, D], table row -> [length, H, D]; an fp8 cache is dequantised to fp32"""
+    """cache [blocks, H, 64, D], table row -> [length, H, D]; an fp8 / MXFP4 cache is dequantised to fp32"""
     nb = (length + 63) // 64
     blocks = cache[block_table[:nb].long()]  # [nb, H, 64, D]
     if is_fp8_kv(cache):
         blocks = dequant_kv_fp8(blocks, scale)
-    return blocks.permute(0, 2, 1, 3).reshape(nb * 64, cache.shape[1], cache.shape[3])[:length]
+    elif is_mxfp4_kv(cache):
+        blocks = dequant_kv_mxfp4_blocks(blocks)
+    return blocks.permute(0, 2, 1, 3).reshape(nb * 64, cache.shape[1], blocks.shape[3])[:length]
 
 
 def kv_dequant_blocks(k_cache, v_cache, phys, k_out, v_out, k_scale=1.0, v_scale=1.0):
-    """scratch block i = dequantised fp8 cache block phys[i] (k_out / v_out [capacity, H, 64, D])."""
+    """scratch block i = dequantised fp8 / MXFP4 cache block phys[i] (k_out / v_out [capacity, H, 64, D])."""
     n = int(phys.numel())
     if n > k_out.shape[0]:
         raise ValueError(f"kv_dequant_blocks: {n} blocks do not fit the scratch capacity {k_out.shape[0]}")
+    if is_mxfp4_kv(k_cache):
+        k_out[:n] = dequant_kv_mxfp4_blocks(k_cache[phys.long()], k_out.dtype)
+        v_out[:n] = dequant_kv_mxfp4_blocks(v_cache[phys.long()], v_out.dtype)
+        return
     k_out[:n] = dequant_kv_fp8(k_cache[phys.long()], k_scale, k_out.dtype)
     v_out[:n] = dequant_kv_fp8(v_cache[phys.long()], v_scale, v_out.dtype)
 
@@ -547,6 +618,17 @@ def decode_attention(q, k_cache, v_cache, block_table, ctx_lens, scale=None, k_s
 
 def kv_write(k, v, k_cache, v_cache, slots, k_scale=1.0, v_scale=1.0):
     _check_kv_pair(k_cache, v_cache)
+    if is_mxfp4_kv(k_cache):  # an MXFP4 cache stores the codes and scale bytes of quantize_kv_mxfp4
+        _check_mxfp4_scales(k_scale, v_scale)
+        for x, cache in ((k, k_cache), (v, v_cache)):
+            codes, sb = quantize_kv_mxfp4(x)
+            pc, ps = mxfp4_kv_planes(cache)
+            for t in range(x.shape[0]):
+                s = int(slots[t])
+                if s >= 0:
+                    pc[s // 64, :, s % 64] = codes[t]
+                    ps[s // 64, :, s % 64] = sb[t]
+        return
     if is_fp8_kv(k_cache):  # an fp8 cache stores the codes of quantize_kv_fp8
         k, v = quantize_kv_fp8(k, k_scale), quantize_kv_fp8(v, v_scale)
     for t in range(k.shape[0]):
